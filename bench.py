@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the fused thermo pipeline on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|p3|wetbulb|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|p3|wetbulb|...] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one 0.1-degree global field
 (3600 x 1800 x 137 fp32 grid points per variable) resident in HBM: one launch of
@@ -11,8 +11,12 @@ torch.distributed.run); grid points are independent, so ranks share nothing and
 the only communication is the timing barrier / max-reduce, done over gloo on the
 CPU so that PyTorch never touches the GPUs the HIP library is using.
 
-Rank 0 prints ONE JSON line: the contract fields plus `roofline` (algorithmic
-bytes / HIP-event kernel time against the 8 TB/s HBM peak), `cpu_baseline` (the
+A plain run sets up, warms up, times the K steps, writes a fixed sample of the last step's outputs if --dump-outputs
+is given, and prints ONE JSON line (rank 0): the contract fields (`value`, `ms_per_step`, ...) and `roofline` from the
+HIP events of the timed steps (algorithmic bytes / kernel time against the 8 TB/s HBM peak); the other figures are null.
+
+With --full the line also carries what takes work beyond the timed steps: `roofline` traffic and VALU counts from
+rocprofv3 child passes, the stream ceiling and the buffer-set spread, `sustained`, `cpu_baseline` (the
 NumPy oracle timed on this box's host cores on a bounded sample, N = 1 only) and
 `parity` (GPU output vs the oracle: the whole 8-level slab SURVEY.md 8d names, 51.84 M points of the timed arrays,
 through a pool of host processes, with the wet-bulb's regime-flip count; plus 256-point windows of 32 levels),
@@ -82,6 +86,12 @@ def parse():
                          "N > 1); weak: one full global field per GPU (the only reading at N = 1, and its label there)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--levels", type=int, default=NLEV, help="levels per field (137 = the named config)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<output>.npy in the run's dtype: all of "
+                         "rank 0's points when they are at most 1 Mi per output, else the same seeded 256 windows of 4096 points")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the timed steps (CPU baseline, parity, end_to_end, buffer sets, stream "
+                         "ceiling, sustained, rocprofv3 counter passes), as the options below set them; without it they are off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-slab-levels", type=int, default=8,
                     help="levels (1800 x 3600 points each) of the slab the single-core CPU baseline runs on")
@@ -114,7 +124,14 @@ def parse():
                     help="independently allocated copies of the input/output fields the kernel is timed on (the first is the timed "
                          "region's; the others add roofline.frac_min/median/max: where a 3.5-GB field lands in HBM moves a "
                          "streaming kernel by 5-10 %%); N = 1, 1 = skip")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does only what `value` and `ms_per_step` need
+        args.no_cpu_baseline, args.traffic, args.valu, args.stream_ceiling = True, "none", "none", False
+        args.sustain, args.parity_slab_levels, args.end_to_end, args.buffer_sets = 0.0, 0, False, 1
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -496,6 +513,9 @@ def main():
     barrier_skew_ms = (max(v[0] for v in stamps) - min(v[0] for v in stamps)) * 1e3
     end_skew_ms = (max(v[1] for v in stamps) - min(v[1] for v in stamps)) * 1e3
 
+    if args.dump_outputs and not args.dry_run and dist.rank == 0:
+        dump_outputs(args.dump_outputs, args.workload, outs)
+
     ndev_seen, dev_used, my_ms = -1, -1, float("nan")
     sustained = None
     if not args.dry_run:
@@ -533,7 +553,7 @@ def main():
         ndev_seen, dev_used = ndev, dev
     # parity: rank 0 judges a sample of its own shard AND, at N > 1, a sample of the LAST rank's shard (whose first point is
     # not point 0 of the field), which travels through the gather together with the sample's place in the global field
-    smp = None if args.dry_run else sample_shard(args, t, q, p, plev, outs, sh, nlev, np_dtype, hyb)
+    smp = None if args.dry_run or not args.full else sample_shard(args, t, q, p, plev, outs, sh, nlev, np_dtype, hyb)
     slab, e2e, sets = None, None, None
     if not args.dry_run and dist.world == 1:
         # the additional legs must never cost the run its line: a failure is reported in its place (and makes parity.ok false
@@ -597,7 +617,7 @@ def main():
             ceiling_streams = (len(fields_in), len(outs))
     last_smp = dist.gather_object(smp if dist.rank == dist.world - 1 else None)
     parity_last, shard_window = None, None
-    if not args.dry_run and dist.rank == 0:
+    if smp is not None and dist.rank == 0:
         parity = judge_sample(args, smp)
         if slab is not None:
             # the slab is THE parity figure of the line; the windows (32 levels of the whole column) stay beside it
@@ -724,6 +744,29 @@ def main():
             line["dry_run"] = True
         print(json.dumps(line), flush=True)
     dist.close()
+
+
+# what each workload's entry point writes, in the order of its output arguments (ekm_thermo.h)
+OUTPUT_NAMES = {"full": ("theta", "es", "rh", "td", "theta_e", "tw"), "p3": ("es", "td", "rh"), "wetbulb": ("tw",),
+                "wetbulb_bisect": ("tw",), "wetbulb_bisect_bolton35": ("tw",), "wetbulb_bisect_bolton39": ("tw",), "rh": ("rh",),
+                "theta": ("theta",), "svp": ("es",), "ept": ("theta_e",), "hybrid_levels": ("p_full",), "geopotential": ("z",)}
+DUMP_WINDOWS, DUMP_WINDOW = 256, 4096  # 1 Mi points per output: the six fp64 outputs of "full" are 48 MB
+
+
+def dump_outputs(path, workload, outs):
+    """The outputs of the last timed step as <path>/<name>.npy: every point of a shard of at most 1 Mi points, else the same
+    DUMP_WINDOWS windows of DUMP_WINDOW points at seeded places, in ascending order (the inputs are seeded too, so two builds
+    compare point for point)."""
+    os.makedirs(path, exist_ok=True)
+    n = outs[0].size
+    if n <= DUMP_WINDOWS * DUMP_WINDOW:
+        starts, width = [0], n
+    else:
+        rng = np.random.default_rng(20260313)
+        starts = np.sort(rng.choice(n // DUMP_WINDOW, DUMP_WINDOWS, replace=False)) * DUMP_WINDOW
+        width = DUMP_WINDOW
+    for name, o in zip(OUTPUT_NAMES[workload], outs):
+        np.save(os.path.join(path, f"{name}.npy"), np.concatenate([o.flat_slice(int(s), int(s) + width).to_host() for s in starts]))
 
 
 CENSUS_KIND = {"full": ("full", 5), "p3": ("p3", None), "wetbulb": ("wetbulb", 0), "wetbulb_bisect": ("bisect", None),

@@ -283,7 +283,7 @@ def _run_two_ranks(ek, extra, shared=True, levels="16"):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--levels", levels, "--sustain", "0.2"] + extra
+           "--levels", levels, "--full", "--sustain", "0.2"] + extra
     if shared and ek.device_count() < 2:
         cmd.append("--allow-shared-device")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=dict(os.environ, OMP_NUM_THREADS="1"))
@@ -374,7 +374,7 @@ def test_bench_measures_its_hbm_traffic_in_the_run(ek):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--levels", "16", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--levels", "16", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -405,6 +405,39 @@ def test_bench_measures_its_hbm_traffic_in_the_run(ek):
     e = d["end_to_end"]
     assert e["points"] == 8 * 1800 * 3600 and e["arrays_in"] == 3 and e["arrays_out"] == 6, e
     assert 0 < e["kernel_ms"] < e["h2d_ms"] < e["d2h_ms"] and e["call_ms"] < e["phases_sum_ms"] * 1.5 and 10 < e["gbs"] < 120, e
+
+
+def test_bench_plain_run_dumps_the_last_step(ek, tmp_path):
+    """A plain bench.py run (no --full) reports the timed steps only, and --dump-outputs writes the seeded sample of what
+    the timed launch computed: the same points the library's own call gives on the same generated inputs."""
+    import argparse
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--levels", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] * 3 - d["timed_region_ms"]) <= 1e-3 * d["timed_region_ms"] + 1e-3
+    assert d["parity"] is None and d["cpu_baseline"] is None and d["sustained"] is None and d["end_to_end"] is None
+    names = ("theta", "es", "rh", "td", "theta_e", "tw")
+    assert sorted(os.listdir(out)) == sorted(f"{n}.npy" for n in names)
+    sys.path.insert(0, root)
+    import bench
+
+    args = argparse.Namespace(workload="full", pmode="field", dtype="f32", scaling="weak", levels=2)
+    sh = bench.plan_shard("full", "field", "weak", 0, 1, 2)
+    t, q, p, _, _ = bench.build_inputs(args, sh, 0, 2, np.float32, 20260313)
+    want = tmp_path / "want"
+    bench.dump_outputs(str(want), "full", list(ek.thermo.pipeline_full(t, q, p)))
+    for n in names:
+        g, w = np.load(out / f"{n}.npy"), np.load(want / f"{n}.npy")
+        assert g.dtype == np.float32 and g.size == bench.DUMP_WINDOWS * bench.DUMP_WINDOW, (n, g.dtype, g.size)
+        assert np.array_equal(g, w, equal_nan=True), n
 
 
 def test_concurrent_calls_from_several_threads(ek):

@@ -5,10 +5,10 @@
 OUT=${1:?out.jsonl}; shift
 : > "$OUT"
 for wl in full p3 wetbulb wetbulb_bisect wetbulb_bisect_bolton35 wetbulb_bisect_bolton39 theta rh ept svp; do
-  timeout -k 10 150 python3 bench.py --workload $wl --dtype f64 --steps 10 --warmup 3 --no-cpu-baseline --traffic none --valu measure --sustain 0 "$@" >> "$OUT" 2>> "$OUT.err" || echo "{\"failed\": \"$wl\"}" >> "$OUT"
+  timeout -k 10 150 python3 bench.py --full --workload $wl --dtype f64 --steps 10 --warmup 3 --no-cpu-baseline --traffic none --valu measure --sustain 0 "$@" >> "$OUT" 2>> "$OUT.err" || echo "{\"failed\": \"$wl\"}" >> "$OUT"
 done
 for pm in level hybrid; do
-  timeout -k 10 150 python3 bench.py --workload full --pmode $pm --dtype f64 --steps 10 --warmup 3 --no-cpu-baseline --traffic none --valu measure --sustain 0 "$@" >> "$OUT" 2>> "$OUT.err" || echo "{\"failed\": \"full $pm\"}" >> "$OUT"
+  timeout -k 10 150 python3 bench.py --full --workload full --pmode $pm --dtype f64 --steps 10 --warmup 3 --no-cpu-baseline --traffic none --valu measure --sustain 0 "$@" >> "$OUT" 2>> "$OUT.err" || echo "{\"failed\": \"full $pm\"}" >> "$OUT"
 done
 python3 - "$OUT" <<'PY'
 import json, sys
