@@ -81,7 +81,7 @@ int device_cus(int dev) {
   return g_cus[dev];
 }
 
-static std::atomic<int> g_tuning_user_set{0};  // ekm_set_tuning was called (or EKM_TILES / EKM_UNROLL set): launch heuristics stand back
+static std::atomic<int> g_tuning_user_set{0};  // ekm_set_tuning has set a value: launch_map's size heuristics stand back, for the rest of the process (nothing clears it)
 int tuning_user_set() { return g_tuning_user_set.load(std::memory_order_relaxed); }
 int tuning_tiles_per_block() { return g_tiles_per_block.load(std::memory_order_relaxed); }
 int tuning_unroll() { return g_unroll.load(std::memory_order_relaxed); }

@@ -217,7 +217,10 @@ EKM_API int ekm_graph_destroy(int dev, void* graph_exec);
 
 /* ---- launch tuning (process-wide; defaults are the measured best) ---- */
 /* tiles_per_block: consecutive 4-KiB tiles (256 lanes x 16 B) one workgroup streams per field;
- * unroll: tiles in flight per lane per trip (1 or 2; the bisection functions' tree-walk kernels always take 1).  0 keeps a value. */
+ * unroll: tiles in flight per lane per trip (1 or 2; the bisection functions' tree-walk kernels always take 1).  0 keeps a value.
+ * The first call that sets either value also switches off, for the rest of the process, the size heuristics that otherwise pick the
+ * launch shape of long full-field calls (two tiles in flight for the fp32 Newton kernels, four tiles for the fp64 ones): no call
+ * switches them back on, not even ekm_set_tuning(1, 1).  Results do not depend on the launch shape. */
 EKM_API int ekm_set_tuning(int tiles_per_block, int unroll);
 EKM_API int ekm_get_tuning(int* tiles_per_block, int* unroll);
 /* secondary parameters by name (defaults from the environment, in brackets):
