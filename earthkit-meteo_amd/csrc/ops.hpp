@@ -18,9 +18,6 @@
 #ifndef EKM_TREE_THREADS
 #define EKM_TREE_THREADS 512
 #endif
-#ifndef EKM_WAVES_PER_EU_DEFAULT
-#define EKM_WAVES_PER_EU_DEFAULT EKM_WAVES_PER_EU
-#endif
 #ifndef EKM_P5_WAVES
 #define EKM_P5_WAVES 5
 #endif
@@ -233,25 +230,8 @@ struct BisectOp : BisectTable<METHOD> {
 #pragma unroll
     for (int j = 0; j < V; ++j) Derived::template prep<T, true>(x[j], te[j], lte[j], p[j], kl[j]);
     if constexpr (sizeof(T) == 4) {
-#if defined(EKM_WALK_SPLIT)  // A/B (round 6, NEGATIVE: 3.08 -> 3.17 ms): the four points of a lane's chunk as two walks of two -- 57
-      // registers instead of 64 and no recomputed thr0, but two LDS reads in flight per wave instead of four (profiles/r06_tree_walk.txt)
-      if constexpr (V == 4) {
-        T l2[2], t2[2], p2[2], k2[2], o2[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            l2[j] = lte[2 * h + j];
-            t2[j] = te[2 * h + j];
-            p2[j] = p[2 * h + j];
-            k2[j] = kl[2 * h + j];
-          }
-          t_on_ma_bisect_heap<METHOD, 2>(l2, t2, p2, k2, tab, o2, all_exact);
-          out[2 * h] = o2[0];
-          out[2 * h + 1] = o2[1];
-        }
-      } else
-#endif
+      // four points per walk at eight waves per SIMD is the optimum: two and eight points per walk measured 3 % and 8 %
+      // slower (profiles/r06_tree_walk.txt (b3), (b4))
       t_on_ma_bisect_heap<METHOD, V>(lte, te, p, kl, tab, out, all_exact);
     }
     else  // double / fd64: sign tests in fp32 on the tree behind the fp64 lattice table, ambiguous steps in T
@@ -455,14 +435,10 @@ struct OpPipelineFull {
     y[2] = T(100.0) * e * m_rcp(es);                  // thermo.py:556
     y[3] = td;
     y[4] = the;
-#ifdef EKM_P5_NOWB  // diagnostic build: how long do the nine streams take with the wet-bulb arithmetic removed?
-    y[5] = the + P.l;
-#else
     // thermo.py:1081-1159; te = theta_e*(p/p0)^kappa = t*exp(K0*q/t_lcl): the pressure powers cancel
     const TeFromTQP<T> exact{t, q, p};
     y[5] = t_on_ma_newton_ifs_core(m_log2(t * T(1.0 / 273.16)) + xe, p, P.dinv, [&] { return t * ex; },
                                    [&] { return m_exp2(T(k::kappa) * P.l); }, exact, tie);
-#endif
   }
 };
 
@@ -526,17 +502,9 @@ struct OpThreads {
   static constexpr bool tree = OpTable<Op>::elems > 0 && OpTable<Op>::vectorized;
   // the fp32 IFS walk with 16-B records: 64 KiB, two 1024-thread workgroups = eight waves per SIMD (<= 64 registers)
   static constexpr bool wide = tree && sizeof(T) == 4 && OpTreeMethod<Op>::value == EPT_IFS && heap_rec<EPT_IFS, float>() == 4;
-#if defined(EKM_WALK_V8)
-  static constexpr int value = wide ? 512 : tree ? EKM_TREE_THREADS : EKM_THREADS_DEFAULT;  // A/B: map_kernel.hpp::map_fields
-#else
   static constexpr int value = wide ? 1024 : tree ? EKM_TREE_THREADS : EKM_THREADS_DEFAULT;
-#endif
   // else fp32: 48 KiB, three workgroups = six waves per SIMD (<= 80 registers); fp64: 80 KiB, two workgroups = four waves
-#if defined(EKM_WALK_V8)
-  static constexpr int field_waves = wide ? 4 : tree ? (sizeof(T) == 4 ? EKM_TREE_WAVES : 4) : EKM_WAVES_PER_EU;
-#else
   static constexpr int field_waves = wide ? 8 : tree ? (sizeof(T) == 4 ? EKM_TREE_WAVES : 4) : EKM_WAVES_PER_EU;
-#endif
 };
 
 // Waves per SIMD a kernel of this op should be compiled for (launch bounds: caps the register allocation).
@@ -546,7 +514,7 @@ struct OpThreads {
 // per-level kernels fit (87-94 VGPRs, no scratch: map_kernel.hpp::map_levels::run_points, tests/test_isa_resources.py).
 template <class Op>
 struct OpWaves {
-  static constexpr int value = EKM_WAVES_PER_EU_DEFAULT;
+  static constexpr int value = EKM_WAVES_PER_EU;
 };
 template <>
 struct OpWaves<OpPipelineFull> {

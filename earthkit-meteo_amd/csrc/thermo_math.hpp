@@ -150,84 +150,21 @@ EKM_HD float m_pow(float x, float y) { return std::pow(x, y); }
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(EKM_F64_LIBM)
 // fp64 on gfx950: there is no fp64 transcendental unit and the device libm pays for correctly rounded
 // results (pow alone is ~200 instructions).  Measured issue cost (tools/microbench/valu_rates_f64.hip):
-// v_fma_f64 5.2 clk per wave, v_rcp_f64 17 clk.  The parity bar for fp64 is 1e-6 relative, so by default
-// the three primitives are built to ~1e-10 (four orders inside the bar; the GPU tests assert <= 1e-9 against the
-// reference's fp64 goldens):
+// v_fma_f64 5.2 clk per wave, v_rcp_f64 17 clk.  The parity bar for fp64 is 1e-6 relative, so the three primitives are
+// built to ~1e-10 (four orders inside the bar; the GPU tests assert <= 1e-9 against the reference's fp64 goldens):
 //   rcp  = v_rcp_f64 seed + ONE Newton step (<= 1e-14);
 //   exp2 = round-to-nearest split + degree-7 near-minimax polynomial of 2^f, ln 2 folded in + v_ldexp_f64 (4.0e-11);
 //   log2 = v_frexp + 2*atanh(s), s = (m-1)/(m+1), as s*q(s^2) with a degree-4 near-minimax q (4.2e-12);
 //   pow  = exp2(y*log2(x)).
-// -DEKM_F64_EXACT selects the <= 3e-16 versions (two Newton steps, degree-12 Taylor, atanh series to s^21)
-// for A/B comparison.  inf / 0 / NaN behave as in libm in both.
-#if defined(EKM_F64_EXACT)
-EKM_HD double m_rcp(double x) {
-  const double r0 = __builtin_amdgcn_rcp(x);
-  double e = __builtin_fma(-x, r0, 1.0);
-  double r = __builtin_fma(r0, e, r0);
-  e = __builtin_fma(-x, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  return __builtin_isfinite(r) ? r : r0;  // x = 0, inf, NaN: keep the hardware answer (inf, 0, NaN)
-}
-EKM_HD double m_div(double a, double b) { return a * m_rcp(b); }
-EKM_HD double m_exp2(double x) {
-  const double xc = __builtin_fmin(__builtin_fmax(x, -1100.0), 1100.0);
-  const double n = __builtin_rint(xc);
-  const double y = (xc - n) * 0.69314718055994530942;  // |y| <= 0.3466
-  double p = 1.0 / 479001600.0;                          // Taylor of e^y, degree 12
-  p = __builtin_fma(p, y, 1.0 / 39916800.0);
-  p = __builtin_fma(p, y, 1.0 / 3628800.0);
-  p = __builtin_fma(p, y, 1.0 / 362880.0);
-  p = __builtin_fma(p, y, 1.0 / 40320.0);
-  p = __builtin_fma(p, y, 1.0 / 5040.0);
-  p = __builtin_fma(p, y, 1.0 / 720.0);
-  p = __builtin_fma(p, y, 1.0 / 120.0);
-  p = __builtin_fma(p, y, 1.0 / 24.0);
-  p = __builtin_fma(p, y, 1.0 / 6.0);
-  p = __builtin_fma(p, y, 0.5);
-  p = __builtin_fma(p, y, 1.0);
-  p = __builtin_fma(p, y, 1.0);
-  const double r = __builtin_amdgcn_ldexp(p, (int)n);
-  return x != x ? x : r;
-}
-EKM_HD double m_log2(double x) {
-  int e = __builtin_amdgcn_frexp_exp(x);
-  double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
-  if (m < 0.70710678118654752440) {
-    m *= 2.0;
-    e -= 1;
-  }
-  const double s = (m - 1.0) * m_rcp(m + 1.0);  // |s| <= 0.1716
-  const double z = s * s;
-  double p = 1.0 / 21.0;                           // atanh series: ln(m) = 2s(1 + z/3 + z^2/5 + ...)
-  p = __builtin_fma(p, z, 1.0 / 19.0);
-  p = __builtin_fma(p, z, 1.0 / 17.0);
-  p = __builtin_fma(p, z, 1.0 / 15.0);
-  p = __builtin_fma(p, z, 1.0 / 13.0);
-  p = __builtin_fma(p, z, 1.0 / 11.0);
-  p = __builtin_fma(p, z, 1.0 / 9.0);
-  p = __builtin_fma(p, z, 1.0 / 7.0);
-  p = __builtin_fma(p, z, 1.0 / 5.0);
-  p = __builtin_fma(p, z, 1.0 / 3.0);
-  p = __builtin_fma(p, z, 1.0);
-  double r = __builtin_fma(p * s, 2.0 * 1.44269504088896340736, (double)e);
-  if (x == 0.0) r = -__builtin_inf();
-  if (x == __builtin_inf()) r = x;
-  if (x < 0.0 || x != x) r = __builtin_nan("");
-  return r;
-}
-#else
-// Shared pieces of the default (~1e-10) set.  The polynomial coefficients live in constant memory, NOT in the
-// instruction stream: v_fma_f64 cannot take a 64-bit literal, so with literal coefficients the compiler materialises
-// each one with two v_mov_b32 in front of a v_fmac_f64 (122 v_mov per point in the six-output pipeline, ~10 % of its
-// issue time; profiles/r03).  Read through the scalar cache they are SGPR pairs, loaded once per wave, that
-// v_fma_f64 takes directly as its addend.  (static: one copy per translation unit / device module.)
-// Round 5 measured one degree less in each polynomial (-DEKM_F64_R5_POLY: exp2 degree 6, 1.9e-9; atanh degree 3, 6.9e-10):
-// the six-output pipeline 14.5 -> 14.2 ms, the Newton wet-bulb 10.2 -> 10.0 -- and row 470 of the reference's own 480-row
-// table beyond the bar (bolton35's one Newton step, whose dlnf cancels to 1e-5 of its terms there, amplifies a primitive's
-// error a thousandfold: 1.8e-6 against 1e-6).  Two per cent are not worth a miss on the reference's own test data: the
-// default keeps round 4's degree 7 / 4 (4.0e-11 / 4.2e-12).  Nor can the reciprocal drop its Newton step: raw v_rcp_f64 is
-// 4.6e-8 (tools/microbench/f64_seed_accuracy.hip) and feeds exponents of up to 40 in es.
-#if !defined(EKM_F64_R5_POLY)
+// inf / 0 / NaN behave as in libm.
+// The polynomial coefficients live in constant memory, NOT in the instruction stream: v_fma_f64 cannot take a 64-bit
+// literal, so with literal coefficients the compiler materialises each one with two v_mov_b32 in front of a v_fmac_f64
+// (122 v_mov per point in the six-output pipeline, ~10 % of its issue time; profiles/r03).  Read through the scalar
+// cache they are SGPR pairs, loaded once per wave, that v_fma_f64 takes directly as its addend.  (static: one copy per
+// translation unit / device module.)
+// One degree less in each polynomial gains 2 % and puts row 470 of the reference's own 480-row table beyond the bar
+// (profiles/HISTORY.md, "Cheaper primitives: measured, not adopted").  Nor can the reciprocal drop its Newton step: raw
+// v_rcp_f64 is 4.6e-8 (tools/microbench/f64_seed_accuracy.hip) and feeds exponents of up to 40 in es.
 static __constant__ double kF64Coef[16] = {
     // 2^f on |f| <= 0.5, degree 7, near-minimax in relative error (4.0e-11), ln 2 folded in; ascending
     0.9999999999616818, 0.693147180728452, 0.24022651198156714, 0.05550410353429554, 0.009618027253757476,
@@ -235,44 +172,23 @@ static __constant__ double kF64Coef[16] = {
     // atanh(s)/s on z = s^2 in [0, 0.0295], degree 4 (4.2e-12); ascending
     1.0000000000041798, 0.3333333262373743, 0.20000192337193154, 0.14267525468490147, 0.1180818033212343,
     0.0, 0.0, 0.0};
-#else
-static __constant__ double kF64Coef[16] = {
-    // 2^f on |f| <= 0.5, degree 6, minimax in relative error (1.86e-9), ln 2 folded in; ascending
-    1.0000000005541665, 0.6931472057372673, 0.2402264689063404, 0.05550328776965614, 0.00961848895713086,
-    0.0013399931219141663, 0.0001534581199765244, 0.0,
-    // atanh(s)/s on z = s^2 in [0, 0.0295], degree 3, minimax in relative error (6.9e-10); ascending
-    0.9999999993106649, 0.3333340797542721, 0.19987397462507944, 0.14962825347475195, 0.0,
-    0.0, 0.0, 0.0};
-#endif
-#if defined(EKM_F64_COEF_LITERAL)
-#error "EKM_F64_COEF_LITERAL was a round-3 A/B switch; the coefficients live in constant memory"
-#endif
-#define EKM_F64C(i) (kF64Coef[i])
 EKM_HD double exp2_poly(double f) {  // 2^f, |f| <= 0.5
-#if !defined(EKM_F64_R5_POLY)
-  double p = EKM_F64C(7);
-  p = __builtin_fma(p, f, EKM_F64C(6));
-#else
-  double p = EKM_F64C(6);
-#endif
-  p = __builtin_fma(p, f, EKM_F64C(5));
-  p = __builtin_fma(p, f, EKM_F64C(4));
-  p = __builtin_fma(p, f, EKM_F64C(3));
-  p = __builtin_fma(p, f, EKM_F64C(2));
-  p = __builtin_fma(p, f, EKM_F64C(1));
-  p = __builtin_fma(p, f, EKM_F64C(0));
+  double p = kF64Coef[7];
+  p = __builtin_fma(p, f, kF64Coef[6]);
+  p = __builtin_fma(p, f, kF64Coef[5]);
+  p = __builtin_fma(p, f, kF64Coef[4]);
+  p = __builtin_fma(p, f, kF64Coef[3]);
+  p = __builtin_fma(p, f, kF64Coef[2]);
+  p = __builtin_fma(p, f, kF64Coef[1]);
+  p = __builtin_fma(p, f, kF64Coef[0]);
   return p;
 }
 EKM_HD double atanh_poly(double z) {  // atanh(s)/s, z = s^2
-#if !defined(EKM_F64_R5_POLY)
-  double p = EKM_F64C(12);
-  p = __builtin_fma(p, z, EKM_F64C(11));
-#else
-  double p = EKM_F64C(11);
-#endif
-  p = __builtin_fma(p, z, EKM_F64C(10));
-  p = __builtin_fma(p, z, EKM_F64C(9));
-  p = __builtin_fma(p, z, EKM_F64C(8));
+  double p = kF64Coef[12];
+  p = __builtin_fma(p, z, kF64Coef[11]);
+  p = __builtin_fma(p, z, kF64Coef[10]);
+  p = __builtin_fma(p, z, kF64Coef[9]);
+  p = __builtin_fma(p, z, kF64Coef[8]);
   return p;
 }
 // v_cvt_i32_f64 saturates (+-2^31, NaN -> 0); the C cast is undefined out of range
@@ -340,7 +256,6 @@ EKM_HD fdouble m_log2(fdouble x) {
   const bool good = __builtin_amdgcn_class(x.v, 0x080 | 0x100);  // +denormal | +normal
   return fdouble(__hiloint2double(good ? __double2hiint(r) : 0x7ff80000, __double2loint(r)));
 }
-#endif
 EKM_HD double m_exp(double x) { return m_exp2(x * 1.44269504088896340736); }
 EKM_HD double m_log(double x) { return m_log2(x) * 0.69314718055994530942; }
 EKM_HD double m_pow(double x, double y) { return m_exp2(y * m_log2(x)); }
@@ -360,7 +275,7 @@ EKM_HD fdouble m_exp(fdouble x) { return m_exp2(x * fdouble(1.442695040888963407
 EKM_HD fdouble m_log(fdouble x) { return m_log2(x) * fdouble(0.69314718055994530942); }
 EKM_HD fdouble m_pow(fdouble x, fdouble y) { return m_exp2(y * m_log2(x)); }
 #else
-// fdouble where the fast primitives do not exist (host twin; -DEKM_F64_EXACT / -DEKM_F64_LIBM device builds): the plain
+// fdouble where the fast primitives do not exist (host twin; -DEKM_F64_LIBM device builds): the plain
 // function of this build, poisoned under exactly the conditions under which the gfx950 composition above poisons, so
 // that the two-pass logic is what the CPU tests exercise (tests/test_hosttwin_two_pass.py).
 EKM_HD bool fd_rcp_ok(double x) { return x != 0.0 && __builtin_isfinite(x) && __builtin_isfinite(1.0 / x); }
@@ -872,104 +787,60 @@ constexpr double kHeapTau0 = 2.5e-6, kHeapTau1 = 1.2e-6;
 
 // Two layouts of the tree (REC = floats of table per node):
 //   3  4096 (es, a) pairs, then the 4096 L: 48 KiB, one ds_read_b64 + one ds_read_b32 per node (two address shifts);
-//   4  4096 records (es, a, L, t_m) of 16 B: 64 KiB, ONE ds_read_b128 per node (one shift, one LDS instruction less per
-//      step and point; t_m spares the exact branch the lattice arithmetic).  Two 1024-thread workgroups with 64 KiB each
-//      fill a CU with 8 waves per SIMD at <= 64 registers: the fp32 IFS walk (ops.hpp::OpThreads).  The Bolton walks need
-//      more registers than that and the fp64 walks carry the fp64 lattice beside the tree: both keep layout 3.
-#ifndef EKM_HEAP_REC_IFS
-#define EKM_HEAP_REC_IFS 4
-#endif
-#ifndef EKM_HEAP_B128
-#define EKM_HEAP_B128 1    // 1: the record in one ds_read_b128; 0: ds_read_b64 + ds_read_b32 from the one address (A/B:
-#endif                     // 3.32 against 3.21 ms; merged by the compiler into ONE ds_read_b96 when L sits right behind a: 3.73)
-#ifndef EKM_HEAP_L_SLOT
-#define EKM_HEAP_L_SLOT 3  // record = (es, a, b, L)
-#endif
-// A/B (round 6, NEGATIVE: 3.07 against 3.02 ms): the fourth float of the 16-byte record as b_m = kHeapTau1*|a_m|, the node's own
-// share of the tolerance band, so that the band of a step is ONE fma on values the step has anyway, b_m + (kHeapTau0/eps)*
-// w_m  (w_m = p + (eps - 1)*es_m >= eps*p wherever es_m <= p), instead of the product kHeapTau0*p -- recomputed at every
-// step for want of a register at the 64-VGPR cap -- and an fma: 8 -> 7 vector instructions per step and point in the
-// static code, but the band is 1/eps = 1.6 x wider in its pressure part, the exact branch is entered that much more
-// often, and the EXECUTED count went up, 130.9 -> 139.1 per point (profiles/r06_tree_walk.txt).  0 (default): round 5's
-// band, kHeapTau1*|a_m| + kHeapTau0*p, and the slot holds t_m.
-#ifndef EKM_HEAP_BAND_SLOT
-#define EKM_HEAP_BAND_SLOT 0
-#endif
-// A/B only (per-depth attribution of LDS conflict cycles, tools/pmc_bisect_depth.sh): the walk stops after this many steps
+//   4  4096 records (es, a, t_m, L) of 16 B: 64 KiB, ONE ds_read_b128 per node (one shift, one LDS instruction less per
+//      step and point; t_m fills the record, the walks form it from the node index).  Two 1024-thread workgroups with
+//      64 KiB each fill a CU with 8 waves per SIMD at <= 64 registers: the fp32 IFS walk (ops.hpp::OpThreads).  The
+//      Bolton walks need more registers than that and the fp64 walks carry the fp64 lattice beside the tree: both keep
+//      layout 3.
+// Plain heap order, one vector load, the band computed per step: a ds_read_b64 + ds_read_b32 pair from the record's
+// address (+3 %), L right behind a (merged into a ds_read_b96: +16 %), the records of depths >= 8 swizzled against bank
+// conflicts (+10 %) and the band's |a_m| share kept in the record (+2 %) all measured slower (profiles/r05_tree_walk.txt
+// (5), profiles/r06_tree_walk.txt (b1), (b2)).
+constexpr int kRecEs = 0, kRecA = 1, kRecT = 2, kRecL = 3;  // the 16-byte record
+// sweep knob (per-depth attribution of LDS conflict cycles, tools/pmc_bisect_depth.sh): the walk stops after this many steps
 #ifndef EKM_WALK_DEPTH
 #define EKM_WALK_DEPTH 12
 #endif
 template <int METHOD, class T>
 constexpr int heap_rec() {
-  return (METHOD == EPT_IFS && sizeof(T) == 4) ? EKM_HEAP_REC_IFS : 3;
+  return (METHOD == EPT_IFS && sizeof(T) == 4) ? 4 : 3;
 }
 struct HeapNode {
-  float es, a, L, b;  // b: the record's fourth float (16-byte records only), else 0
+  float es, a, L;
 };
-// A/B only (profiles/r06_tree_walk.txt): the records of depths >= 8 -- where the LDS bank conflicts
-// are, 96 % of them in the last four steps -- stored at idx ^ ((idx >> 4) & 15), so that nodes 16 apart stop sharing the
-// banks of a 16-byte slot.  The collisions there are random (a wave's lanes scatter over hundreds of leaves of the noisy
-// benchmark field), a permutation of the slots cannot change their statistics, and the three extra instructions per deep
-// step cost more than nothing: 0 (default) = plain heap order.
-#ifndef EKM_HEAP_SWIZZLE
-#define EKM_HEAP_SWIZZLE 0
-#endif
-EKM_HD unsigned heap_slot(unsigned node) {
-#if EKM_HEAP_SWIZZLE
-  return node >= 256u ? node ^ ((node >> 4) & 15u) : node;
-#else
-  return node;
-#endif
-}
 template <int REC>
 EKM_HD HeapNode heap_read(const float* __restrict__ tab, unsigned node) {
   HeapNode r;
-  if (REC == 4) node = heap_slot(node);
 #if defined(__HIP_DEVICE_COMPILE__)
   const char* __restrict__ base = reinterpret_cast<const char*>(tab);
   if (REC == 4) {
-#if EKM_HEAP_B128
     typedef float f4 __attribute__((ext_vector_type(4)));
     const f4 v = *reinterpret_cast<const f4*>(base + (node << 4));  // one ds_read_b128 (a register tuple of four per point)
-    r.es = v[0];
-    r.a = v[1];
-    r.L = v[EKM_HEAP_L_SLOT];
-    r.b = v[5 - EKM_HEAP_L_SLOT];
-#else
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const char* __restrict__ rec = base + (node << 4);  // ONE address: ds_read_b64 + ds_read_b32 offset:12
-    const f2 ea = *reinterpret_cast<const f2*>(rec);
-    r.es = ea[0];
-    r.a = ea[1];
-    r.L = *reinterpret_cast<const float*>(rec + 4 * EKM_HEAP_L_SLOT);
-    r.b = EKM_HEAP_BAND_SLOT ? *reinterpret_cast<const float*>(rec + 4 * (5 - EKM_HEAP_L_SLOT)) : 0.0f;
-#endif
+    r.es = v[kRecEs];
+    r.a = v[kRecA];
+    r.L = v[kRecL];
   } else {
     typedef float f2 __attribute__((ext_vector_type(2)));
     const f2 ea = *reinterpret_cast<const f2*>(base + (node << 3));  // one ds_read_b64
     r.es = ea[0];
     r.a = ea[1];
     r.L = *reinterpret_cast<const float*>(base + 8 * kHeapNodes + (node << 2));
-    r.b = 0.0f;
   }
 #else
   if (REC == 4) {
-    r.es = tab[4 * node];
-    r.a = tab[4 * node + 1];
-    r.L = tab[4 * node + EKM_HEAP_L_SLOT];
-    r.b = tab[4 * node + (5 - EKM_HEAP_L_SLOT)];
+    r.es = tab[4 * node + kRecEs];
+    r.a = tab[4 * node + kRecA];
+    r.L = tab[4 * node + kRecL];
   } else {
     r.es = tab[2 * node];
     r.a = tab[2 * node + 1];
     r.L = tab[2 * kHeapNodes + node];
-    r.b = 0.0f;
   }
 #endif
   return r;
 }
 template <int REC>
 EKM_HD float heap_es(const float* __restrict__ tab, unsigned node) {
-  if (REC == 4) node = heap_slot(node);
   return tab[(REC == 4 ? 4 : 2) * node];
 }
 
@@ -1000,11 +871,11 @@ EKM_HD void bisect_heap_fill(float* __restrict__ tab, int i) {
     }
   }
   if (REC == 4) {
-    const int s = (int)heap_slot((unsigned)i);  // (a permutation within each aligned group of 16 records)
-    tab[4 * s] = es;
-    tab[4 * s + 1] = a;
-    tab[4 * s + EKM_HEAP_L_SLOT] = L;
-    tab[4 * s + (5 - EKM_HEAP_L_SLOT)] = EKM_HEAP_BAND_SLOT ? float(kHeapTau1) * __builtin_fabsf(a) : t;
+    float* __restrict__ rec = tab + 4 * i;
+    rec[kRecEs] = es;
+    rec[kRecA] = a;
+    rec[kRecT] = t;
+    rec[kRecL] = L;
   } else {
     tab[2 * i] = es;
     tab[2 * i + 1] = a;
@@ -1034,11 +905,7 @@ EKM_HD unsigned bisect_heap_child(unsigned node, float nr) {
 // with u = L_m - le, le = log2(theta_e/273.16) (`te` is theta_e itself for these methods; `kl` is read for bolton35 only).
 // D of one node (fp32): positive <=> the residual is positive, unless |D| <= the band (then `amb`); returned NEGATED.  w = the positive
 // denominator the exact step divides by (ifs: p + (eps-1)*es; Bolton: p - es); thr0 = the part of the band that goes with p.
-constexpr double kB35WsExact = 2.0;
-#ifndef EKM_B35_FOLD
-#define EKM_B35_FOLD 1  // kl folded into the logarithm the walk carries (A/B: 0 subtracts it at every step)
-#endif
-
+constexpr double kB35WsExact = 2.0;  // ws from which bolton35 is searched again step by step (t_on_ma_bisect_heap)
 
 // The reference's bolton35 residual as it stands, theta_e*exp(G_sat(scale=-1)) - th_sat (thermo.py:1075, 1215-1224), in
 // base 2: theta_e*2^(a_m*ws) - t_m*2^(kl*(0.28*ws - 1)), a_m = -2675*log2(e)/t_m, kl = kappa*log2(p/p0).  NOT divided by
@@ -1073,11 +940,10 @@ EKM_HD float bisect_exact_residual(float es, float a, float w, float te, float t
   return m_fms(te, METHOD == EPT_IFS ? m_exp2(g) : m_exp2_denorm(g), tm);
 }
 
-// WS: test ws >= kB35WsExact at every node (A/B only: both walks ask once, of the hottest node they visited)
-template <int METHOD, bool WS = false, bool F64 = false, bool BAND_SLOT = false>
-EKM_HD float bisect_fast_test(float es, float a, float u, float p, float kl, float& w, float thr0, bool& amb, float b = 0.0f) {
+template <int METHOD, bool F64 = false>
+EKM_HD float bisect_fast_test(float es, float a, float u, float p, float kl, float& w, float thr0, bool& amb) {
   float D, scale;  // D: MINUS the quantity of the comments above (bisect_heap_child takes it so); scale: |a_m| resp. its
-  bool big_ws = false;  // counterpart -- the part of the band that goes with the size of the exponent
+                   // counterpart -- the part of the band that goes with the size of the exponent
   if (METHOD == EPT_IFS) {
     w = m_fma(float(k::eps - 1), es, p);
     D = m_fms(u, w, a);
@@ -1086,13 +952,7 @@ EKM_HD float bisect_fast_test(float es, float a, float u, float p, float kl, flo
     w = p - es;
     const float ees = float(k::eps) * es;
     scale = ees * m_fnma(0.28f, kl, a);
-    D = m_fms(EKM_B35_FOLD ? u : u - kl, w, scale);  // u = L_m - (le + kl): the walks fold kl into the logarithm they carry
-    // ws = eps*es/(p - es) >= kB35WsExact: the reference's two terms, theta_e*exp(-2675*ws/t) and th_sat =
-    // t*(p0/p)^(kappa*(1 - 0.28*ws)), can BOTH leave the normal range there (ws of several hundred where p - es is a
-    // fraction of a pascal: 0 - 0, sign 0, the reference stays on this node for good), and D -- the residual divided
-    // by th_sat/t -- no longer says what the reference's own subtraction gives.  Below the limit both terms are
-    // normal numbers (|exponents| <= 29*2 resp. 47*1.56) and the division changes nothing.  Decided by the exact step.
-    if (WS) big_ws = !(w > float(kB35WsExact) * ees);
+    D = m_fms(u, w, scale);  // u = L_m - (le + kl): the walks fold kl into the logarithm they carry
   } else {
     w = p - es;
     const float ees = float(k::eps) * es;
@@ -1106,11 +966,7 @@ EKM_HD float bisect_fast_test(float es, float a, float u, float p, float kl, flo
     // more than the band above knows of -- dD = dw*(2*w*|X| + kappa/ln2*w + |a|*eps*es)
     if (F64) thr0 = m_fma(1.5e-7f * p, m_fma(w, m_fma(2.0f, __builtin_fabsf(X), 0.5f), __builtin_fabsf(aees)), thr0);
   }
-  if (METHOD == EPT_IFS && BAND_SLOT)  // b = kHeapTau1*|a_m| from the record; (kHeapTau0/eps)*w >= kHeapTau0*p (EKM_HEAP_BAND_SLOT)
-    amb = !(__builtin_fabsf(D) > m_fma(w, float(kHeapTau0 / k::eps), b));
-  else
-    amb = !(__builtin_fabsf(D) > m_fma(__builtin_fabsf(scale), float(METHOD == EPT_IFS ? kHeapTau1 : 2.0 * kHeapTau1), thr0));  // NaN: ambiguous
-  if (METHOD == EPT_BOLTON35 && WS) amb = amb || big_ws;
+  amb = !(__builtin_fabsf(D) > m_fma(__builtin_fabsf(scale), float(METHOD == EPT_IFS ? kHeapTau1 : 2.0 * kHeapTau1), thr0));  // NaN: ambiguous
   return D;
 }
 
@@ -1158,17 +1014,16 @@ EKM_HD void t_on_ma_bisect_heap(const float (&lte)[V], const float (&te)[V], con
     // reference where the logarithmic test reads +inf: with a NaN logarithm every test of such a point is NaN, i.e.
     // ambiguous, and every step takes the reference's own residual
     lq[j] = (METHOD != EPT_IFS && !(lte[j] < std::numeric_limits<float>::infinity())) ? nan_v<float>() : lte[j];
-    // a NEGATIVE te (a temperature handed over in Celsius) has no logarithm; the reference's residual te*2^g - t_m is
+    // a negative te (a temperature handed over in Celsius) has no logarithm; the reference's residual te*2^g - t_m is
     // negative at every node then, as for te = 0: the same walk (all the way down, 133.19 K), not NaN
     if (METHOD == EPT_IFS && te[j] < 0.0f) lq[j] = -std::numeric_limits<float>::infinity();
-    if (METHOD == EPT_BOLTON35 && EKM_B35_FOLD) lq[j] += kl[j];  // bolton35's test takes u - kl (bisect_fast_test)
+    if (METHOD == EPT_BOLTON35) lq[j] += kl[j];  // bolton35's test takes u - kl: folded in once (2.8 % over subtracting it per step, profiles/r05_tree_walk.txt)
     tfix[j] = 0.0f;
   }
   constexpr int REC = heap_rec<METHOD, float>();
-  constexpr bool BAND_SLOT = METHOD == EPT_IFS && REC == 4 && EKM_HEAP_BAND_SLOT;
 #pragma unroll
   for (int d = 0; d < EKM_WALK_DEPTH; ++d) {
-    float es[V], a[V], w[V], D[V], L[V], b[V];
+    float es[V], a[V], w[V], D[V], L[V];
     bool amb[V];
     unsigned long long any = 0ull;  // lanes of the wave with an ambiguous test at this depth, over the V points
     // (forcing all table reads of a step out before the first is waited for -- the compiler pairs the points, two LDS
@@ -1179,12 +1034,11 @@ EKM_HD void t_on_ma_bisect_heap(const float (&lte)[V], const float (&te)[V], con
       es[j] = nd.es;
       a[j] = nd.a;
       L[j] = nd.L;
-      b[j] = nd.b;
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const float u = L[j] - lq[j];
-      D[j] = bisect_fast_test<METHOD, false, false, BAND_SLOT>(es[j], a[j], u, p[j], kl[j], w[j], thr0[j], amb[j], b[j]);
+      D[j] = bisect_fast_test<METHOD>(es[j], a[j], u, p[j], kl[j], w[j], thr0[j], amb[j]);
       any |= EKM_WAVE_MASK(amb[j]);
       amb[j] = amb[j] || all_exact;
     }
@@ -1320,7 +1174,7 @@ EKM_HD void t_on_ma_bisect_heap64(const T (&lte)[V], const T (&te)[V], const T (
     thr0[j] = float(1.5 * kHeapTau0) * pf[j];
     if (METHOD != EPT_IFS && !(ltef[j] < std::numeric_limits<float>::infinity())) ltef[j] = nan_v<float>();  // as in the fp32 walk
     if (METHOD == EPT_IFS && te[j] < T(0.0)) ltef[j] = -std::numeric_limits<float>::infinity();              // likewise
-    if (METHOD == EPT_BOLTON35 && EKM_B35_FOLD) ltef[j] += klf[j];
+    if (METHOD == EPT_BOLTON35) ltef[j] += klf[j];
     tfix[j] = T(0.0);
   }
   constexpr int REC = heap_rec<METHOD, double>();
@@ -1335,7 +1189,7 @@ EKM_HD void t_on_ma_bisect_heap64(const T (&lte)[V], const T (&te)[V], const T (
       const float es = nd.es, a = nd.a;
       const float u = nd.L - ltef[j];
       float w;
-      D[j] = bisect_fast_test<METHOD, false, true>(es, a, u, pf[j], klf[j], w, thr0[j], amb[j]);  // (the band is wide enough for
+      D[j] = bisect_fast_test<METHOD, true>(es, a, u, pf[j], klf[j], w, thr0[j], amb[j]);  // (the band is wide enough for
       any |= EKM_WAVE_MASK(amb[j]);                                                         //  the inputs' rounding to float)
       amb[j] = amb[j] || all_exact;
     }
