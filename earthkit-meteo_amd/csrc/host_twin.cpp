@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "interp_point.hpp"
 #include "ops.hpp"
 
 // Ops that keep a per-workgroup LDS table on the device (ops.hpp::OpTable, the bisection lattice) take the SAME path
@@ -74,3 +75,67 @@ static int host_map(const T* const* ins, T* const* outs, size_t n, double rp) {
 static int host_bad_enum(const char*, ...) { return -3; }
 
 #include "gen/host_entries.inc"
+
+// ---- vertical interpolation: the column routine of interp.hip (interp_point.hpp) on the CPU, same arguments as the
+// ekm_interpolate_* entry points of include/ekm_thermo.h without dev / stream ----
+template <class T, bool FUSED>
+static int host_interp(const T* data, const T* coord, int coord_is_field, const T* A, const T* B, const T* sp,
+                       const T* target, int target_is_field, unsigned ntarget, size_t npts, unsigned nlev, int descending,
+                       int mode, const T* const (&aux)[4], unsigned aux_field_mask, T* out) {
+  if (nlev < 2 || mode < 0 || mode > 2) return -2;
+  for (unsigned t = 0; t < ntarget; ++t) {
+    for (size_t i = 0; i < npts; ++i) {
+      const T tc = target_is_field ? target[(size_t)t * npts + i] : target[t];
+      auto coord_of = [&](unsigned m) -> T {
+        if (FUSED) return ekm::hybrid_p_full(A[m], B[m], A[m + 1], B[m + 1], sp[i]);
+        return coord_is_field ? coord[(size_t)m * npts + i] : coord[m];
+      };
+      auto data_of = [&](unsigned m) -> T { return data[(size_t)m * npts + i]; };
+      ekm::InterpAux<T> lay[2];
+      for (int e = 0; e < 2; ++e) {
+        lay[e].on = aux[2 * e] && aux[2 * e + 1];
+        lay[e].data = lay[e].coord = T(0);
+        if (lay[e].on) {
+          lay[e].data = aux[2 * e][(aux_field_mask >> (2 * e)) & 1 ? i : 0];
+          lay[e].coord = aux[2 * e + 1][(aux_field_mask >> (2 * e + 1)) & 1 ? i : 0];
+        }
+      }
+      const unsigned idx = ekm::interp_bracket<T>(nlev, descending, tc, coord_of);
+      out[(size_t)t * npts + i] = ekm::interp_value<T>(idx, nlev, descending, mode, tc, coord_of, data_of, lay[1], lay[0]);
+    }
+  }
+  return 0;
+}
+
+#define EKM_HOST_INTERP(tag, T)                                                                                      \
+  extern "C" int ekm_host_interpolate_monotonic_##tag(                                                               \
+      const T* data, const T* coord, int coord_is_field, const T* target, int target_is_field, unsigned ntarget,     \
+      size_t npts, unsigned nlev, int descending, int mode, const T* aux_min_data, const T* aux_min_coord,           \
+      const T* aux_max_data, const T* aux_max_coord, unsigned aux_field_mask, T* out) {                              \
+    const T* const aux[4] = {aux_min_data, aux_min_coord, aux_max_data, aux_max_coord};                              \
+    return host_interp<T, false>(data, coord, coord_is_field, nullptr, nullptr, nullptr, target, target_is_field,    \
+                                 ntarget, npts, nlev, descending, mode, aux, aux_field_mask, out);                   \
+  }                                                                                                                  \
+  extern "C" int ekm_host_interpolate_hybrid_to_pressure_##tag(                                                      \
+      const T* data, const T* A, const T* B, const T* sp, const T* target, int target_is_field, unsigned ntarget,    \
+      size_t npts, unsigned nfull, int descending, int mode, const T* aux_min_data, const T* aux_min_coord,          \
+      const T* aux_max_data, const T* aux_max_coord, unsigned aux_field_mask, T* out) {                              \
+    const T* const aux[4] = {aux_min_data, aux_min_coord, aux_max_data, aux_max_coord};                              \
+    return host_interp<T, true>(data, nullptr, 0, A, B, sp, target, target_is_field, ntarget, npts, nfull,           \
+                                descending, mode, aux, aux_field_mask, out);                                         \
+  }
+#define EKM_HOST_HEIGHT(tag, T)                                                                                      \
+  extern "C" int ekm_host_height_from_geopotential_##tag(const T* z, const T* zs, size_t npts, unsigned nlev, int mode, \
+                                                         T* out) {                                                   \
+    if (mode < 2 || mode > 5) return -3;                                                                             \
+    for (unsigned k = 0; k < nlev; ++k)                                                                              \
+      for (size_t i = 0; i < npts; ++i)                                                                              \
+        out[k * npts + i] = ekm::height_from_geopotential<T>(z[k * npts + i], mode >= 4 ? zs[i] : T(0), mode);       \
+    return 0;                                                                                                        \
+  }
+EKM_HOST_HEIGHT(f32, float)
+EKM_HOST_HEIGHT(f64, double)
+#undef EKM_HOST_HEIGHT
+EKM_HOST_INTERP(f32, float)
+EKM_HOST_INTERP(f64, double)
+#undef EKM_HOST_INTERP

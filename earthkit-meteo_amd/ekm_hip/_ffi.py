@@ -81,6 +81,11 @@ def _signatures():
         sig[f"ekm_any_le_{tag}"] = ([i, vp, vp, sz, real, real, real, vp], i)
         sig[f"ekm_geopotential_on_hybrid_levels_{tag}"] = ([i, vp, vp, vp, vp, vp, vp, vp, sz, u32, i, real, i, vp], i)
         sig[f"ekm_geopotential_thickness_from_alpha_delta_{tag}"] = ([i, vp, vp, vp, vp, vp, sz, u32, vp], i)
+        sig[f"ekm_interpolate_monotonic_{tag}"] = (
+            [i, vp, vp, vp, i, vp, i, u32, sz, u32, i, i, vp, vp, vp, vp, u32, vp], i)
+        sig[f"ekm_height_from_geopotential_{tag}"] = ([i, vp, vp, vp, sz, u32, i, vp], i)
+        sig[f"ekm_interpolate_hybrid_to_pressure_{tag}"] = (
+            [i, vp, vp, vp, vp, vp, vp, i, u32, sz, u32, i, i, vp, vp, vp, vp, u32, vp], i)
     for name, (ins, outs, ints, has_eps) in OPS.items():
         for tag, real in (("f32", C.c_float), ("f64", C.c_double)):
             args = [i, vp] + [C.POINTER(Operand)] * len(ins) + [i] * len(ints)

@@ -199,10 +199,11 @@ _GEO_MODE = {"thickness": 0, "geopotential": 1, ("geometric", "sea"): 2, ("geopo
              ("geometric", "ground"): 4, ("geopotential", "ground"): 5}
 
 
-def _chain(t, q, zs, A, B, sp, alpha_top, mode, vertical_axis):
+def _chain(t, q, zs, A, B, sp, alpha_top, mode, vertical_axis, device_result=False):
     """t, q on hybrid full levels + surface pressure -> geopotential thickness / geopotential / height in
     ONE bottom-up pass per column (vertical.py:741-1190); alpha, delta and the half-level pressures are
-    formed on the fly and never stored."""
+    formed on the fly and never stored.  `device_result`: the level-major field stays in device memory whatever the
+    inputs were (it feeds the interpolation kernel), rounded to the dtype a NumPy caller would have got."""
     if alpha_top not in ["ifs", "arpege"]:
         raise ValueError(f"Unknown method '{alpha_top}' for pressure calculation. Use 'ifs' or 'arpege'.")
     A, B = np.asarray(A), np.asarray(B)
@@ -260,8 +261,12 @@ def _chain(t, q, zs, A, B, sp, alpha_top, mode, vertical_axis):
     if on_device:
         _ffi.check(lib.ekm_stream_sync(device, current_stream()))
         return out
+    if device_result and out_dtype == dtype:
+        return out
     res = out.to_host().astype(out_dtype, copy=False)
     out.free()
+    if device_result:  # mixed dtypes: the field a NumPy caller gets is rounded to t's and q's dtype
+        return DeviceArray.from_host(res, device)
     if vertical_axis != 0:
         res = np.moveaxis(res, 0, vertical_axis)
     return res
@@ -333,6 +338,308 @@ def height_on_hybrid_levels(t, q, zs, A, B, sp, alpha_top="ifs", h_type="geometr
         raise ValueError(f"Unknown '{h_reference=}'. Use 'sea' or 'ground'.")
     key = ("geometric" if h_type == "geometric" else "geopotential", h_reference)
     return _chain(t, q, zs, A, B, sp, alpha_top, _GEO_MODE[key], vertical_axis)
+
+
+# ---- vertical interpolation (vertical/array/vertical.py:1206-1719, vertical/array/monotonic.py) ----
+_INTERP_MODE = {"linear": 0, "log": 1, "nearest": 2}
+
+
+def _arith_dtype(parts):
+    """f32 only when every array taking part is f32, f64 otherwise (NumPy promotion of data, coord, target and aux)."""
+    return _F32 if np.result_type(*parts, np.float32) == _F32 else _F64
+
+
+def _to_device(x, dtype, device, shape=None):
+    """`x` (DeviceArray or NumPy) as a contiguous DeviceArray of `dtype`; a DeviceArray of another dtype goes through the host."""
+    if isinstance(x, DeviceArray):
+        if x.dtype == dtype:
+            return x
+        x = x.to_host()
+    x = np.asarray(x, dtype=dtype)
+    if shape is not None:
+        x = np.broadcast_to(x, shape)
+    return DeviceArray.from_host(np.ascontiguousarray(x), device)
+
+
+def _interp_check(interpolation, data, coord_shape, target, vertical_axis, on_device):
+    """The argument checks of monotonic.py:63-122 on shapes alone (no device call): returns (nlev, columns shape)."""
+    if interpolation not in _INTERP_MODE:
+        raise ValueError(f"Unknown interpolation method '{interpolation}'. Supported methods are 'linear', 'log' and 'nearest'.")
+    if on_device and vertical_axis != 0:
+        raise ValueError("DeviceArray input: fields are level-major, vertical_axis must be 0")
+    dshape, tshape = tuple(data.shape), tuple(target.shape)
+    if len(dshape) == 0 or dshape[0] < 2:
+        raise ValueError("At least two levels are required for interpolation.")
+    if dshape[0] != coord_shape[0]:
+        raise ValueError(f"The first dimension of data and that of coord must match! {dshape=} {coord_shape=}")
+    same = dshape == tuple(coord_shape)
+    if same:
+        if len(dshape) == 1 and len(tshape) != 1:
+            raise ValueError("If values and p have the same shape, they cannot both be scalars.")
+        if len(dshape) > 1 and len(tshape) != 1 and dshape[1:] != tshape[1:]:
+            raise ValueError("When values and target_p have different shapes, target_p must be a scalar or a 1D array.")
+    elif len(coord_shape) != 1:
+        raise ValueError(f"When values and p have different shapes, p must be a scalar or a 1D array. {dshape=} {coord_shape=}")
+    elif len(tshape) != 1 and (dshape[-1] != dshape[0] or dshape[1:] != tshape[1:]):
+        # the reference broadcasts the level vector along the LAST axis and transposes (monotonic.py:143): that works
+        # only where the last axis is as long as the level axis, and fails to broadcast everywhere else
+        raise ValueError("A 1D coord needs a scalar or 1D target_coord (or data whose last axis is as long as its level axis).")
+    return dshape[0], dshape[1:]
+
+
+def _interp_run(data, target, interpolation, aux, descending, dtype, out_dtype, device, cols, coord=None, hybrid=None):
+    """Upload what is not on the device yet, launch the generic kernel (`coord`) or the fused hybrid->pressure one
+    (`hybrid` = (A, B, sp)), and hand the [ntarget, *cols] result back as a DeviceArray of the arithmetic dtype."""
+    nlev, npts = int(data.shape[0]), int(math.prod(cols))
+    stream = current_stream()
+    keep = []  # device buffers of this call: alive until the launch is enqueued
+
+    def dev(x, shape=None):
+        d = _to_device(x, dtype, device, shape)
+        d.on(stream)
+        keep.append(d)
+        return d
+
+    d_data = dev(data)
+    t_field = len(target.shape) != 1
+    d_target = dev(target)
+    ntarget = int(target.shape[0])
+    ptrs, mask = [], 0
+    for e, (ad, ac) in enumerate(aux):  # (min_data, min_coord), (max_data, max_coord)
+        if ad is None or ac is None:
+            ptrs += [None, None]
+            continue
+        for b, x in enumerate((ad, ac)):
+            size = int(math.prod(x.shape)) if isinstance(x, DeviceArray) else np.size(x)
+            if size == 1:
+                ptrs.append(dev(x if isinstance(x, DeviceArray) else np.reshape(x, (1,))).ptr)
+            else:
+                if isinstance(x, DeviceArray) and tuple(x.shape) != tuple(cols):
+                    raise ValueError(f"aux array of shape {tuple(x.shape)} does not match a level of data {tuple(cols)}")
+                ptrs.append(dev(x, cols).ptr)
+                mask |= 1 << (2 * e + b)
+    out = DeviceArray.empty((ntarget,) + tuple(cols), dtype, device)
+    lib = _ffi.lib()
+    tag = "f32" if dtype == _F32 else "f64"
+    mode = _INTERP_MODE[interpolation]
+    if hybrid is not None:
+        d_a, d_b, d_sp = (dev(x) for x in hybrid)
+        _ffi.check(getattr(lib, f"ekm_interpolate_hybrid_to_pressure_{tag}")(
+            device, stream, d_data.ptr, d_a.ptr, d_b.ptr, d_sp.ptr, d_target.ptr, int(t_field), ntarget, npts, nlev,
+            int(descending), mode, ptrs[0], ptrs[1], ptrs[2], ptrs[3], mask, out.on(stream)))
+    else:
+        c_field = len(coord.shape) != 1 or npts == 1 and len(cols) == 0
+        d_coord = dev(coord)
+        _ffi.check(getattr(lib, f"ekm_interpolate_monotonic_{tag}")(
+            device, stream, d_data.ptr, d_coord.ptr, int(c_field), d_target.ptr, int(t_field), ntarget, npts, nlev,
+            int(descending), mode, ptrs[0], ptrs[1], ptrs[2], ptrs[3], mask, out.on(stream)))
+    return out
+
+
+def _interp_finish(out, on_device, out_dtype, vertical_axis):
+    if on_device:
+        return out
+    res = out.to_host().astype(out_dtype, copy=False)
+    out.free()
+    if vertical_axis != 0 and res.ndim > 1:
+        res = np.moveaxis(res, 0, vertical_axis)
+    return res
+
+
+def _host_or_dev(x, atleast_1d=False):
+    if x is None or isinstance(x, DeviceArray):
+        return x
+    return np.atleast_1d(x) if atleast_1d else np.asarray(x)
+
+
+def _first_two_ends(coord, device):
+    """coord[0] and coord[-1] of the first column (monotonic.py:84-89); two elements read back for a DeviceArray."""
+    if not isinstance(coord, DeviceArray):
+        flat = coord.reshape(coord.shape[0], -1)
+        return flat[0, 0], flat[-1, 0]
+    lib, stream = _ffi.lib(), current_stream()
+    coord.on(stream)
+    host = np.zeros(2, coord.dtype)
+    row = int(math.prod(coord.shape[1:])) * coord.dtype.itemsize
+    item = coord.dtype.itemsize
+    _ffi.check(lib.ekm_d2h(device, host.ctypes.data, coord.ptr, item, stream))
+    _ffi.check(lib.ekm_d2h(device, host.ctypes.data + item, coord.ptr + (coord.shape[0] - 1) * row, item, stream))
+    _ffi.check(lib.ekm_stream_sync(device, stream))
+    return host[0], host[1]
+
+
+def _out_dtype(data):
+    """The result has data's dtype; non-floating data is computed and returned in f64 (the reference writes NaN into an
+    integer array there: the one typing deviation)."""
+    return np.dtype(data.dtype) if np.dtype(data.dtype) in (_F32, _F64, np.dtype(np.float16)) else _F64
+
+
+@_foreign_aware("data", "coord", "target_coord", "aux_min_level_data", "aux_min_level_coord", "aux_max_level_data",
+                "aux_max_level_coord")
+def interpolate_monotonic(data, coord, target_coord, interpolation="linear", aux_min_level_data=None,
+                          aux_min_level_coord=None, aux_max_level_data=None, aux_max_level_coord=None, vertical_axis=0):
+    """Interpolate `data` between levels of a monotonic coordinate (vertical.py:1616-1719, monotonic.py:49-370):
+    'linear', 'log' or 'nearest', NaN outside the column unless an aux layer reaches the target.
+
+    NumPy in -> NumPy out; DeviceArray in -> DeviceArray out (level-major, `vertical_axis` must be 0).  The arithmetic
+    runs in f32 when data, coord, target_coord and the aux arrays are all f32 and in f64 otherwise.  A NumPy result has
+    `data`'s dtype, except that non-floating data gives f64 (the reference writes NaN into an integer array there).
+    A DeviceArray result stays in the ARITHMETIC dtype (f32 data with an f64 coord gives f64), as the device results of
+    the other `vertical` functions do: the second typing deviation.  A DeviceArray argument of another dtype than the
+    arithmetic one is converted on the host, which makes the call wait for the device.
+    The ordering of the levels is read from the first column, as in the reference; nothing is flipped in memory.
+    With a 1D `coord`, multi-dimensional `data` and a scalar or 1D target the aux layers are not used
+    (monotonic.py:299-358).  A 1D `coord` with a multi-dimensional target raises ValueError where the reference fails to
+    broadcast it (monotonic.py:143), which is everywhere except where data's last axis is as long as its level axis;
+    there the coordinate is the level vector of every column, as in the reference.
+    `vertical_axis` != 0 has its documented meaning in every case: the result's level axis is moved back, also for a 1D
+    `coord` with a 1D target, where the reference returns the levels on axis 0 (monotonic.py:167-170)."""
+    return _monotonic(data, coord, target_coord, interpolation, aux_min_level_data, aux_min_level_coord, aux_max_level_data,
+                      aux_max_level_coord, vertical_axis)
+
+
+def _monotonic(data, coord, target_coord, interpolation, aux_min_level_data, aux_min_level_coord, aux_max_level_data,
+               aux_max_level_coord, vertical_axis, on_device=None):
+    """`interpolate_monotonic`; `on_device` says what the caller was given when `coord` is a device-resident temporary of
+    its own (level-major already) beside NumPy arguments."""
+    data = _host_or_dev(data)
+    coord = _host_or_dev(coord, True)
+    target = _host_or_dev(target_coord, True)
+    aux = [_host_or_dev(x, True) for x in (aux_min_level_data, aux_min_level_coord, aux_max_level_data, aux_max_level_coord)]
+    if on_device is None:
+        on_device = any(isinstance(x, DeviceArray) for x in [data, coord, target] + aux)
+    if interpolation in _INTERP_MODE and not on_device and vertical_axis != 0:
+        data, coord, target = (x if isinstance(x, DeviceArray) or x.ndim <= 1 else np.moveaxis(x, vertical_axis, 0)
+                               for x in (data, coord, target))
+    nlev, cols = _interp_check(interpolation, data, tuple(coord.shape), target, vertical_axis, on_device)
+    if tuple(coord.shape) != tuple(data.shape) and len(target.shape) == 1:
+        aux = [None] * 4  # 1D coord, 1D target, fields of data: the reference's simple_compute knows no aux layers
+    aux = [(aux[0], aux[1]), (aux[2], aux[3])]
+    aux = [(d, c) if d is not None and c is not None else (None, None) for d, c in aux]
+    parts = [x.dtype for x in [data, coord, target] + [x for pair in aux for x in pair] if x is not None]
+    out_dtype = _out_dtype(data)
+    dtype = _arith_dtype(parts + [out_dtype])
+    device = next((x.device for x in [data, coord, target] if isinstance(x, DeviceArray)), current_device())
+    c0, c1 = _first_two_ends(coord, device)
+    out = _interp_run(data, target, interpolation, aux, not bool(c0 < c1), dtype, out_dtype, device, cols, coord=coord)
+    return _interp_finish(out, on_device, out_dtype, vertical_axis)
+
+
+@_foreign_aware("data", "target_p", "sp", "aux_bottom_data", "aux_bottom_p", "aux_top_data", "aux_top_p")
+def interpolate_hybrid_to_pressure_levels(data, target_p, A, B, sp, alpha_top="ifs", interpolation="linear",
+                                          aux_bottom_data=None, aux_bottom_p=None, aux_top_data=None, aux_top_p=None,
+                                          vertical_axis=0):
+    """Interpolate `data` from hybrid full levels to pressure levels (vertical.py:1206-1326) in ONE kernel: the pressure
+    of the model levels is formed from A, B and `sp` inside it (each operation rounded as the reference rounds it) and
+    never stored.  `data` may hold fewer levels than the tables: the bottom-most ones (vertical.py:1191-1203).
+
+    NumPy in -> NumPy out, with `vertical_axis` meaning what the reference documents (the axis is moved in and back;
+    the reference itself raises a shape error there for multi-dimensional data).  DeviceArray in -> DeviceArray out,
+    level-major; with `sp` on the device the call ASSUMES that pressure increases with the level index (true for every
+    table whose half-level pressures do) instead of reading the first column back, so the call enqueues without a host
+    wait -- provided every DeviceArray argument has the arithmetic dtype (one of another dtype is converted on the host).
+    Dtypes as in `interpolate_monotonic`, with A, B and sp taking part in the promotion."""
+    if alpha_top not in ["ifs", "arpege"]:
+        raise ValueError(f"Unknown method '{alpha_top}' for pressure calculation. Use 'ifs' or 'arpege'.")
+    A, B = np.asarray(A), np.asarray(B)
+    data = _host_or_dev(data)
+    sp = _host_or_dev(sp)
+    target = _host_or_dev(target_p, True)
+    # aux_bottom_* lies at the largest pressure (aux_max_level_*), aux_top_* at the smallest (vertical.py:1316-1326)
+    aux = [_host_or_dev(x, True) for x in (aux_top_data, aux_top_p, aux_bottom_data, aux_bottom_p)]
+    on_device = any(isinstance(x, DeviceArray) for x in [data, sp, target] + aux)
+    if interpolation in _INTERP_MODE and not on_device and vertical_axis != 0:
+        data, target = (np.moveaxis(x, vertical_axis, 0) if x.ndim > 1 else x for x in (data, target))
+    nlev_t, cols = _interp_check(interpolation, data, tuple(data.shape), target, vertical_axis, on_device)
+    nlev = A.shape[0] - 1
+    if A.ndim != 1 or A.shape != B.shape or nlev_t > nlev:
+        raise ValueError(f"data have {nlev_t} levels, A/B have {nlev} levels")
+    A, B = A[nlev - nlev_t:], B[nlev - nlev_t:]
+    if isinstance(sp, DeviceArray):
+        if tuple(sp.shape) != tuple(cols) and not (sp.size == 1 and math.prod(cols) == 1):
+            raise ValueError(f"sp {tuple(sp.shape)} does not match a level of data {tuple(cols)}")
+    else:
+        sp = np.broadcast_to(sp, cols)  # ValueError when it cannot
+    aux = [(aux[0], aux[1]), (aux[2], aux[3])]
+    aux = [(d, c) if d is not None and c is not None else (None, None) for d, c in aux]
+    parts = [x.dtype for x in [data, sp, target, A, B] + [x for pair in aux for x in pair] if x is not None]
+    out_dtype = _out_dtype(data)
+    dtype = _arith_dtype(parts + [out_dtype])
+    device = next((x.device for x in [data, sp, target] if isinstance(x, DeviceArray)), current_device())
+    descending = False
+    if not isinstance(sp, DeviceArray) and sp.size:  # the reference's ordering decision on the first column (monotonic.py:84-89)
+        s0 = np.asarray(sp, dtype=dtype).reshape(-1)[:1]
+        a, b = A.astype(dtype), B.astype(dtype)
+        ph = a[[0, 1, -2, -1]] + b[[0, 1, -2, -1]] * s0
+        pf = ph[[0, 2]] + 0.5 * (ph[[1, 3]] - ph[[0, 2]])
+        descending = not bool(pf[0] < pf[1])
+    out = _interp_run(data, target, interpolation, aux, descending, dtype, out_dtype, device, cols, hybrid=(A, B, sp))
+    return _interp_finish(out, on_device, out_dtype, vertical_axis)
+
+
+@_foreign_aware("data", "target_h", "t", "q", "zs", "sp", "aux_bottom_data", "aux_bottom_h", "aux_top_data", "aux_top_h")
+def interpolate_hybrid_to_height_levels(data, target_h, t, q, zs, A, B, sp, alpha_top="ifs", h_type="geometric",
+                                        h_reference="ground", interpolation="linear", aux_bottom_data=None,
+                                        aux_bottom_h=None, aux_top_data=None, aux_top_h=None, vertical_axis=0):
+    """Interpolate `data` from hybrid full levels to height levels (vertical.py:1329-1486): `height_on_hybrid_levels`
+    (one column scan) writing a device-resident height field that feeds the kernel of `interpolate_monotonic`; the
+    height field is never copied to the host, for NumPy input either."""
+    if interpolation not in _INTERP_MODE:
+        raise ValueError(f"Unknown interpolation method '{interpolation}'. Supported methods are 'linear', 'log' and 'nearest'.")
+    if h_reference not in ["sea", "ground"]:
+        raise ValueError(f"Unknown '{h_reference=}'. Use 'sea' or 'ground'.")
+    others = (data, target_h, t, q, zs, sp, aux_bottom_data, aux_bottom_h, aux_top_data, aux_top_h)
+    on_device = any(isinstance(x, DeviceArray) for x in others)
+    if on_device and vertical_axis != 0:
+        raise ValueError("DeviceArray input: fields are level-major, vertical_axis must be 0")
+    key = ("geometric" if h_type == "geometric" else "geopotential", h_reference)
+    h = _chain(t, q, zs, A, B, sp, alpha_top, _GEO_MODE[key], vertical_axis, device_result=True)
+    # aux_bottom_* lies at the smallest height (aux_min_level_*), aux_top_* at the largest (vertical.py:1476-1486)
+    return _monotonic(data, h, target_h, interpolation, aux_bottom_data, aux_bottom_h, aux_top_data, aux_top_h, vertical_axis,
+                      on_device=on_device)
+
+
+@_foreign_aware("data", "target_h", "z", "zs", "aux_bottom_data", "aux_bottom_h", "aux_top_data", "aux_top_h")
+def interpolate_pressure_to_height_levels(data, target_h, z, zs, h_type="geometric", h_reference="ground",
+                                          interpolation="linear", aux_bottom_data=None, aux_bottom_h=None, aux_top_data=None,
+                                          aux_top_h=None, vertical_axis=0):
+    """Interpolate `data` from pressure levels to height levels (vertical.py:1489-1613): the height of the levels is
+    formed from the geopotential `z` (and `zs` for heights above ground) by one elementwise kernel into a device-resident
+    temporary, which feeds `interpolate_monotonic`.  As in the reference, any `h_type` but "geometric" means
+    geopotential height and any `h_reference` but "ground" means above sea level."""
+    if interpolation not in _INTERP_MODE:
+        raise ValueError(f"Unknown interpolation method '{interpolation}'. Supported methods are 'linear', 'log' and 'nearest'.")
+    z, zs_in = _host_or_dev(z), _host_or_dev(zs)
+    others = [_host_or_dev(x) for x in (data, target_h, aux_bottom_data, aux_bottom_h, aux_top_data, aux_top_h)]
+    on_device = any(isinstance(x, DeviceArray) for x in [z, zs_in] + others)
+    if on_device and vertical_axis != 0:
+        raise ValueError("DeviceArray input: fields are level-major, vertical_axis must be 0")
+    if not isinstance(z, DeviceArray) and vertical_axis != 0 and z.ndim > 1:
+        z = np.moveaxis(z, vertical_axis, 0)
+    if len(z.shape) == 0:
+        raise ValueError("At least two levels are required for interpolation.")
+    ground = h_reference == "ground"
+    mode = (4 if ground else 2) if h_type == "geometric" else (5 if ground else 3)
+    cols = tuple(z.shape[1:])
+    parts = [z.dtype] + ([zs_in.dtype] if ground else [])
+    dtype = _arith_dtype(parts) if all(np.dtype(p).kind == "f" for p in parts) else _F64
+    device = next((x.device for x in [z, zs_in] + others if isinstance(x, DeviceArray)), current_device())
+    stream = current_stream()
+    d_z = _to_device(z, dtype, device)
+    d_zs = None
+    if ground:
+        if isinstance(zs_in, DeviceArray) and tuple(zs_in.shape) != cols and not (zs_in.size == 1 and math.prod(cols) == 1):
+            raise ValueError(f"zs {tuple(zs_in.shape)} does not match a level of z {cols}")
+        d_zs = _to_device(zs_in, dtype, device, None if isinstance(zs_in, DeviceArray) else cols)
+        d_zs.on(stream)
+    h = DeviceArray.empty(tuple(z.shape), dtype, device)
+    tag = "f32" if dtype == _F32 else "f64"
+    _ffi.check(getattr(_ffi.lib(), f"ekm_height_from_geopotential_{tag}")(
+        device, stream, d_z.on(stream), d_zs.ptr if d_zs is not None else None, int(math.prod(cols)), int(z.shape[0]), mode,
+        h.on(stream)))
+    # aux_bottom_* lies at the smallest height (aux_min_level_*), aux_top_* at the largest (vertical.py:1603-1613)
+    return _monotonic(data, h, target_h, interpolation, aux_bottom_data, aux_bottom_h, aux_top_data, aux_top_h, vertical_axis,
+                      on_device=on_device)
 
 
 _LEVEL_TABLES = None

@@ -2,8 +2,8 @@
 """Model-level post-processing on an MI355X with the earthkit-meteo signatures.
 
 Temperature and specific humidity on IFS hybrid levels + surface pressure and surface geopotential
--> pressure, relative humidity, dewpoint, theta_e, wet-bulb temperature and geopotential height,
-everything resident in HBM between calls.  Run from the repository root:
+-> pressure, relative humidity, dewpoint, theta_e, wet-bulb temperature and geopotential height, then
+theta_e and relative humidity on pressure levels, everything resident in HBM between calls.  Run from the repository root:
 
     python examples/model_level_postprocessing.py
 """
@@ -39,7 +39,17 @@ def main(nlat=181, nlon=360):
     tw = thermo.wet_bulb_temperature_from_specific_humidity(d_t, d_q, pressure, t_method="newton")
     h = vertical.height_on_hybrid_levels(d_t, d_q, d_zs, A.astype(np.float32), B.astype(np.float32), d_sp,
                                          h_type="geopotential", h_reference="sea")
+    # the pressure-level product: theta_e and rh on 10 pressure levels without leaving HBM (p is formed in the kernel)
+    levels = 100.0 * np.array([1000, 925, 850, 700, 500, 400, 300, 250, 200, 100], dtype=np.float32)
+    a32, b32 = A.astype(np.float32), B.astype(np.float32)
+    theta_e_pl = vertical.interpolate_hybrid_to_pressure_levels(theta_e, levels, a32, b32, d_sp)
+    rh_pl = vertical.interpolate_hybrid_to_pressure_levels(rh, levels, a32, b32, d_sp)
     ekm_hip.synchronize()
+
+    for name, arr in (("theta_e [K]", theta_e_pl), ("rh [%]", rh_pl)):
+        a = arr.to_host()[2]  # NaN where 850 hPa is below the ground
+        print(f"850 hPa    {name:12s} min {np.nanmin(a):10.3f}  mean {np.nanmean(a):10.3f}  max {np.nanmax(a):10.3f}  "
+              f"below ground {np.isnan(a).mean():.1%}")
 
     k = 120  # a level near 900 hPa
     for name, arr in (("p [Pa]", p), ("rh [%]", rh), ("td [K]", td), ("theta_e [K]", theta_e), ("tw [K]", tw),

@@ -309,6 +309,59 @@ EKM_API int ekm_any_le_f32(int dev, void* stream, const float* sp, size_t n, flo
 EKM_API int ekm_any_le_f64(int dev, void* stream, const double* sp, size_t n, double a0, double b0, double thresh,
                            int32_t* flag);
 
+/* ---- vertical interpolation from model levels to pressure / height levels ----
+ * interpolate_monotonic: reference vertical/array/vertical.py:1616-1719 and vertical/array/monotonic.py:49-370.
+ * data: [nlev, npts] level-major; coord: [nlev, npts] (coord_is_field != 0) or [nlev]; target: [ntarget] or
+ * [ntarget, npts] (target_is_field != 0); out: [ntarget, npts].  nlev >= 2, ntarget <= 65535.
+ * descending: the reference's ordering decision (monotonic.py:82-91: coord[0] >= coord[-1] in the first column),
+ *   taken by the caller; nothing is flipped in memory.  A column that is not monotonic gives an unspecified value.
+ * mode: EKM_INTERP_LINEAR / _LOG / _NEAREST.
+ * aux_*: the optional layers beyond the smallest (min) and the largest (max) coordinate of a column; a layer is
+ *   active when both its pointers are given; each is ONE value on the device, or [npts] when its bit of
+ *   aux_field_mask is set (bit 0 min_data, 1 min_coord, 2 max_data, 3 max_coord).
+ * Like every compute entry point these only enqueue a kernel: nothing waits on the host. */
+#define EKM_INTERP_LINEAR 0
+#define EKM_INTERP_LOG 1
+#define EKM_INTERP_NEAREST 2
+EKM_API int ekm_interpolate_monotonic_f32(int dev, void* stream, const float* data, const float* coord,
+                                          int coord_is_field, const float* target, int target_is_field,
+                                          uint32_t ntarget, size_t npts, uint32_t nlev, int descending, int mode,
+                                          const float* aux_min_data, const float* aux_min_coord,
+                                          const float* aux_max_data, const float* aux_max_coord,
+                                          uint32_t aux_field_mask, float* out);
+EKM_API int ekm_interpolate_monotonic_f64(int dev, void* stream, const double* data, const double* coord,
+                                          int coord_is_field, const double* target, int target_is_field,
+                                          uint32_t ntarget, size_t npts, uint32_t nlev, int descending, int mode,
+                                          const double* aux_min_data, const double* aux_min_coord,
+                                          const double* aux_max_data, const double* aux_max_coord,
+                                          uint32_t aux_field_mask, double* out);
+/* The height coordinate of interpolate_pressure_to_height_levels: reference vertical/array/vertical.py:1489-1613
+ * (:1593-1601; geopotential_height_from_geopotential :330-345, geometric_height_from_geopotential :472-501).
+ * z, out: [nlev, npts] level-major; zs: [npts], read by the "above ground" modes only.  mode as in
+ * ekm_geopotential_on_hybrid_levels_*: 2 geometric height above sea, 3 geopotential height above sea, 4 geometric
+ * height above ground, 5 geopotential height above ground.  Every operation rounded once, IEEE division. */
+EKM_API int ekm_height_from_geopotential_f32(int dev, void* stream, const float* z, const float* zs, size_t npts,
+                                             uint32_t nlev, int mode, float* out);
+EKM_API int ekm_height_from_geopotential_f64(int dev, void* stream, const double* z, const double* zs, size_t npts,
+                                             uint32_t nlev, int mode, double* out);
+/* interpolate_hybrid_to_pressure_levels: reference vertical/array/vertical.py:1206-1326, fused with the producer of
+ * the pressure (vertical.py:663, 708): the coordinate is p_full formed in the kernel from sp [npts] and the nfull+1
+ * half-level coefficients A, B of the data's levels, each operation rounded once in the reference's order; the
+ * pressure field is never stored.  aux_min_* is the layer above the model top (the reference's aux_top_*),
+ * aux_max_* the one below the lowest level (aux_bottom_*).  nfull <= 2047 (fp64) / 4095 (fp32). */
+EKM_API int ekm_interpolate_hybrid_to_pressure_f32(int dev, void* stream, const float* data, const float* A,
+                                                   const float* B, const float* sp, const float* target,
+                                                   int target_is_field, uint32_t ntarget, size_t npts, uint32_t nfull,
+                                                   int descending, int mode, const float* aux_min_data,
+                                                   const float* aux_min_coord, const float* aux_max_data,
+                                                   const float* aux_max_coord, uint32_t aux_field_mask, float* out);
+EKM_API int ekm_interpolate_hybrid_to_pressure_f64(int dev, void* stream, const double* data, const double* A,
+                                                   const double* B, const double* sp, const double* target,
+                                                   int target_is_field, uint32_t ntarget, size_t npts, uint32_t nfull,
+                                                   int descending, int mode, const double* aux_min_data,
+                                                   const double* aux_min_coord, const double* aux_max_data,
+                                                   const double* aux_max_coord, uint32_t aux_field_mask, double* out);
+
 /* ---- thermo entry points ----
  * Argument order: dev, stream, inputs..., enum parameters..., [eps], outputs..., n. */
 '''
