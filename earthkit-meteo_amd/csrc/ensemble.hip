@@ -1,0 +1,235 @@
+// Ensemble reductions on gfx950: Extreme Forecast Index, Shift of Tails and CRPS.
+// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82.
+//
+// One kernel family: one lane per grid point, one wave (64 lanes) per workgroup.  The fields are member-major,
+// ens [nens, npts] and clim [nclim, npts], so a wave reads a member row as one coalesced run.  The lane's ensemble is
+// insertion-sorted as it streams in and kept in LDS as [nens][64], lane-minor: the 64 lanes of a step touch 64
+// consecutive words (two per lane in fp64), which is free of bank conflicts whatever slot each lane is at.
+//  * efi:  the climate rows are streamed once, never staged; each row's rank in the sorted ensemble comes from a
+//          cursor that moves on from the previous row's rank (either way, so an unsorted climate is counted right).
+//          Traffic: (nclim + nens) elements read, 8 B written per point.
+//  * sot:  the percentile of the sorted ensemble (numpy's lerp) against two climate rows.
+//  * crps: Hersbach's alpha/beta walk over the sorted ensemble; optional 1-B "missing" flag per point.
+// LDS: nens * 64 * sizeof(T) <= 64 KiB per workgroup: nens <= 256 (fp32) / 128 (fp64); beyond that the entry points
+// return EKM_ERR_ARG.  The per-point arithmetic is ensemble_point.hpp, shared with the host twin.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "../../include/ekm_thermo.h"
+#include "ensemble_point.hpp"
+#include "map_kernel.hpp"
+
+namespace ekm {
+
+constexpr int kEnsLanes = 64;                   // one wave per workgroup
+constexpr size_t kEnsLdsBytes = 64 * 1024;      // the sorted ensembles of a workgroup
+constexpr int kEnsBatch = 8;                    // member rows in flight per lane while sorting
+
+// Streams the nens member rows of point p into the lane's LDS column, sorted ascending; returns "a member is NaN".
+// zero_below: sot.py:88 (members below eps become 0 before the percentile).
+template <class T>
+__device__ __forceinline__ bool sort_members(const T* __restrict__ ens, unsigned nens, unsigned long long npts,
+                                             unsigned long long p, T* col, bool zero_below, T teps) {
+  auto get = [&](unsigned j) -> T { return col[j * kEnsLanes]; };
+  auto set = [&](unsigned j, T v) { col[j * kEnsLanes] = v; };
+  bool has_nan = false;
+  for (unsigned m0 = 0; m0 < nens; m0 += kEnsBatch) {
+    T v[kEnsBatch];
+#pragma unroll
+    for (int b = 0; b < kEnsBatch; ++b)
+      if (m0 + b < nens) v[b] = ens[(unsigned long long)(m0 + b) * npts + p];
+#pragma unroll
+    for (int b = 0; b < kEnsBatch; ++b)
+      if (m0 + b < nens) {
+        T x = v[b];
+        if (zero_below && x < teps) x = T(0);
+        has_nan = has_nan || x != x;
+        ens_insert<T>(m0 + b, x, get, set);
+      }
+  }
+  return has_nan;
+}
+
+template <class T>
+__global__ __launch_bounds__(kEnsLanes) void efi_points(const T* __restrict__ clim, const T* __restrict__ ens,
+                                                        unsigned nclim, unsigned nens, unsigned long long npts,
+                                                        double eps, const double* __restrict__ acosdiff,
+                                                        const double* __restrict__ proddiff,
+                                                        const double* __restrict__ acoef, double* __restrict__ out) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
+  if (p >= npts) return;
+  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
+  const bool has_nan = sort_members<T>(ens, nens, npts, p, col, false, T(0));
+  out[p] = efi_point<T>(
+      nclim, nens, has_nan, [&](unsigned i) -> T { return clim[(unsigned long long)i * npts + p]; },
+      [&](unsigned j) -> T { return col[j * kEnsLanes]; }, acosdiff, proddiff, acoef, eps);
+}
+
+template <class T>
+__global__ __launch_bounds__(kEnsLanes) void sot_points(const T* __restrict__ qc, const T* __restrict__ qc_tail,
+                                                        const T* __restrict__ ens, unsigned nens,
+                                                        unsigned long long npts, Percentile<T> pos, double eps,
+                                                        T* __restrict__ out) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
+  if (p >= npts) return;
+  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
+  const bool has_nan = sort_members<T>(ens, nens, npts, p, col, eps > 0.0, T(eps));
+  out[p] = sot_point<T>(qc[p], qc_tail[p], has_nan, [&](unsigned j) -> T { return col[j * kEnsLanes]; }, pos, eps);
+}
+
+template <class T>
+__global__ __launch_bounds__(kEnsLanes) void crps_points(const T* __restrict__ x, const T* __restrict__ y, unsigned nens,
+                                                         unsigned long long npts, const double* __restrict__ p2,
+                                                         const double* __restrict__ q2, double* __restrict__ out,
+                                                         unsigned char* __restrict__ missing) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
+  if (p >= npts) return;
+  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
+  const bool has_nan = sort_members<T>(x, nens, npts, p, col, false, T(0));
+  const T yp = y[p];
+  const bool miss = has_nan || yp != yp;  // ensemble.py:44
+  const double r = crps_point<T>(nens, yp, [&](unsigned j) -> T { return col[j * kEnsLanes]; }, p2, q2);
+  out[p] = miss ? nan_v<double>() : r;
+  if (missing) missing[p] = miss ? 1 : 0;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void sot_func_points(const T* __restrict__ qc_tail, const T* __restrict__ qc,
+                                                       const T* __restrict__ qf, unsigned long long n, T min_den, T lower,
+                                                       T upper, T* __restrict__ out) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  out[p] = sot_func_point<T>(qc_tail[p], qc[p], qf[p], min_den, lower, upper);
+}
+
+// Common argument checks; returns the grid size in *grid
+template <class T>
+static int ens_prepare(int dev, const char* what, size_t npts, uint32_t nens, std::initializer_list<const void*> ptrs,
+                       unsigned* grid, size_t* lds) {
+  if (nens < 1) return set_error(EKM_ERR_ARG, "%s: at least one member is required", what);
+  *lds = (size_t)nens * kEnsLanes * sizeof(T);
+  if (*lds > kEnsLdsBytes)
+    return set_error(EKM_ERR_ARG, "%s: %u members need %zu B of LDS per workgroup (max %zu: %zu members)", what, nens, *lds,
+                     kEnsLdsBytes, kEnsLdsBytes / (kEnsLanes * sizeof(T)));
+  for (const void* ptr : ptrs) {
+    if (!ptr) return set_error(EKM_ERR_ARG, "%s: null pointer", what);
+    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(T))
+      return set_error(EKM_ERR_ARG, "%s: a pointer is not aligned to its element size (%d B)", what, (int)sizeof(T));
+  }
+  const unsigned long long g = ((unsigned long long)npts + kEnsLanes - 1) / kEnsLanes;
+  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "%s: too many points", what);
+  *grid = (unsigned)g;
+  return use_device(dev);
+}
+
+static int ens_launched(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+  return EKM_OK;
+}
+
+template <class T>
+static int launch_efi(int dev, void* stream, const T* clim, const T* ens, uint32_t nclim, uint32_t nens, size_t npts,
+                      double eps, const double* acosdiff, const double* proddiff, const double* acoef, double* out) {
+  if (npts == 0) return EKM_OK;
+  if (nclim < 1) return set_error(EKM_ERR_ARG, "efi: at least one climate row is required");
+  if (nclim > 1 && (!acosdiff || !proddiff || !acoef)) return set_error(EKM_ERR_ARG, "efi: null coefficient table");
+  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(double)) return set_error(EKM_ERR_ARG, "efi: out is null or not 8-B aligned");
+  unsigned grid;
+  size_t lds;
+  int rc = ens_prepare<T>(dev, "efi", npts, nens, {clim, ens}, &grid, &lds);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL((efi_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), clim, ens, nclim,
+                     nens, (unsigned long long)npts, eps, acosdiff, proddiff, acoef, out);
+  return ens_launched("efi");
+}
+
+template <class T>
+static int launch_sot(int dev, void* stream, const T* qc, const T* qc_tail, const T* ens, uint32_t nens, size_t npts,
+                      int perc, double eps, T* out) {
+  if (npts == 0) return EKM_OK;
+  if (perc < 2 || perc > 98 || perc == 50) return set_error(EKM_ERR_ARG, "sot: perc=%d must be in [2, 98] and not 50", perc);
+  unsigned grid;
+  size_t lds;
+  int rc = ens_prepare<T>(dev, "sot", npts, nens, {qc, qc_tail, ens, out}, &grid, &lds);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL((sot_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), qc, qc_tail, ens,
+                     nens, (unsigned long long)npts, percentile_position<T>(nens, perc), eps, out);
+  return ens_launched("sot");
+}
+
+template <class T>
+static int launch_sot_func(int dev, void* stream, const T* qc_tail, const T* qc, const T* qf, size_t n, double eps,
+                           double lower, double upper, T* out) {
+  if (n == 0) return EKM_OK;
+  for (const void* ptr : {(const void*)qc_tail, (const void*)qc, (const void*)qf, (const void*)out}) {
+    if (!ptr) return set_error(EKM_ERR_ARG, "sot_func: null pointer");
+    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(T)) return set_error(EKM_ERR_ARG, "sot_func: a pointer is not aligned to its element size");
+  }
+  const unsigned long long grid = ((unsigned long long)n + 255) / 256;
+  if (grid > 0x7fffffffull) return set_error(EKM_ERR_ARG, "sot_func: too many points");
+  int rc = use_device(dev);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL((sot_func_points<T>), dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), qc_tail, qc,
+                     qf, (unsigned long long)n, T(eps > 0.0 ? eps : 0.0), T(lower), T(upper), out);
+  return ens_launched("sot_func");
+}
+
+template <class T>
+static int launch_crps(int dev, void* stream, const T* x, const T* y, uint32_t nens, size_t npts, const double* p2,
+                       const double* q2, double* out, uint8_t* missing) {
+  if (npts == 0) return EKM_OK;
+  if (!p2 || !q2) return set_error(EKM_ERR_ARG, "crps_from_ensemble: null weight table");
+  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(double))
+    return set_error(EKM_ERR_ARG, "crps_from_ensemble: out is null or not 8-B aligned");
+  unsigned grid;
+  size_t lds;
+  int rc = ens_prepare<T>(dev, "crps_from_ensemble", npts, nens, {x, y}, &grid, &lds);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL((crps_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), x, y, nens,
+                     (unsigned long long)npts, p2, q2, out, missing);
+  return ens_launched("crps_from_ensemble");
+}
+
+}  // namespace ekm
+
+extern "C" {
+
+int ekm_efi_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens, size_t npts,
+                double eps, const double* acosdiff, const double* proddiff, const double* acoef, double* out) {
+  return ekm::launch_efi<float>(dev, stream, clim, ens, nclim, nens, npts, eps, acosdiff, proddiff, acoef, out);
+}
+int ekm_efi_f64(int dev, void* stream, const double* clim, const double* ens, uint32_t nclim, uint32_t nens, size_t npts,
+                double eps, const double* acosdiff, const double* proddiff, const double* acoef, double* out) {
+  return ekm::launch_efi<double>(dev, stream, clim, ens, nclim, nens, npts, eps, acosdiff, proddiff, acoef, out);
+}
+
+int ekm_sot_f32(int dev, void* stream, const float* qc, const float* qc_tail, const float* ens, uint32_t nens, size_t npts,
+                int perc, double eps, float* out) {
+  return ekm::launch_sot<float>(dev, stream, qc, qc_tail, ens, nens, npts, perc, eps, out);
+}
+int ekm_sot_f64(int dev, void* stream, const double* qc, const double* qc_tail, const double* ens, uint32_t nens,
+                size_t npts, int perc, double eps, double* out) {
+  return ekm::launch_sot<double>(dev, stream, qc, qc_tail, ens, nens, npts, perc, eps, out);
+}
+
+int ekm_sot_func_f32(int dev, void* stream, const float* qc_tail, const float* qc, const float* qf, size_t n, double eps,
+                     double lower_bound, double upper_bound, float* out) {
+  return ekm::launch_sot_func<float>(dev, stream, qc_tail, qc, qf, n, eps, lower_bound, upper_bound, out);
+}
+int ekm_sot_func_f64(int dev, void* stream, const double* qc_tail, const double* qc, const double* qf, size_t n, double eps,
+                     double lower_bound, double upper_bound, double* out) {
+  return ekm::launch_sot_func<double>(dev, stream, qc_tail, qc, qf, n, eps, lower_bound, upper_bound, out);
+}
+
+int ekm_crps_from_ensemble_f32(int dev, void* stream, const float* x, const float* y, uint32_t nens, size_t npts,
+                               const double* p2, const double* q2, double* out, uint8_t* missing) {
+  return ekm::launch_crps<float>(dev, stream, x, y, nens, npts, p2, q2, out, missing);
+}
+int ekm_crps_from_ensemble_f64(int dev, void* stream, const double* x, const double* y, uint32_t nens, size_t npts,
+                               const double* p2, const double* q2, double* out, uint8_t* missing) {
+  return ekm::launch_crps<double>(dev, stream, x, y, nens, npts, p2, q2, out, missing);
+}
+
+}  // extern "C"

@@ -1,0 +1,178 @@
+// Reductions over the member axis of one grid point: Extreme Forecast Index, Shift of Tails and CRPS of an ensemble
+// against a model climate or an analysis.  One statement of the arithmetic for the gfx950 kernels (ensemble.hip) and
+// the host test twin (host_twin.cpp).
+// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82.
+//
+// All three work on the point's ensemble SORTED ascending; `s(j)` below reads sorted member j.  The results are held to
+// the reference bit for bit, so every operation is rounded once in the reference's order: nothing is contracted into
+// an fma (en_* below; the host twin is built with -ffp-contract=off), divisions are IEEE divisions, and the f64 sums
+// run sequentially in the reference's loop order.
+#pragma once
+
+#include <cmath>
+
+#include "thermo_math.hpp"
+
+namespace ekm {
+
+template <class T>
+EKM_HD T en_add(T a, T b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return a + b;
+}
+template <class T>
+EKM_HD T en_sub(T a, T b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return a - b;
+}
+template <class T>
+EKM_HD T en_mul(T a, T b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return a * b;
+}
+
+// numpy.maximum / numpy.minimum: a NaN in either operand comes back
+EKM_HD double en_max(double a, double b) { return (a >= b || a != a) ? a : b; }
+EKM_HD double en_min(double a, double b) { return (a <= b || a != a) ? a : b; }
+
+// Member v goes into the sorted run s[0..k) (insertion from the top).  A NaN stays where it lands: every caller flags
+// a column that holds one and gives it the reference's NaN, so its order is never read.
+template <class T, class Get, class Set>
+EKM_HD void ens_insert(unsigned k, T v, Get get, Set set) {
+  unsigned j = k;
+  while (j > 0) {
+    const T u = get(j - 1);
+    if (!(u > v)) break;
+    set(j, u);
+    --j;
+  }
+  set(j, v);
+}
+
+// efi.py:40-89.  clim(i) is row i of the point's climate, read ONCE each, in order; it need not be sorted: the count
+// of members <= clim(i) (efi.py:49) is the upper-bound rank in the sorted ensemble, found by a cursor that walks either
+// way from the previous row's rank.  frac and dFdp are formed in T (zeros_like(clim), efi.py:46, 51, 55), the terms and
+// the sum in double (the coefficient tables are float64, efi.py:57-60).  acosdiff, proddiff, acoef: nclim-1 values each.
+template <class T, class Clim, class Sorted>
+EKM_HD double efi_point(unsigned nclim, unsigned nens, bool ens_nan, Clim clim, Sorted s, const double* acosdiff,
+                        const double* proddiff, const double* acoef, double eps) {
+  const T tn = T(nens), scale = T(nclim - 1), teps = T(eps);
+  const bool masked = eps > 0.0;
+  unsigned cur = 0;
+  auto rank = [&](T c) -> unsigned {
+    while (cur > 0 && s(cur - 1) > c) --cur;
+    while (cur < nens && s(cur) <= c) ++cur;
+    return cur;
+  };
+  const T c0 = clim(0);
+  bool missing = ens_nan || c0 != c0;
+  T f0 = T(rank(c0)) / tn;
+  double efi = 0.0, efimax = 0.0;
+  for (unsigned icl = 0; icl + 1 < nclim; ++icl) {
+    const T c1 = clim(icl + 1);
+    missing = missing || c1 != c1;
+    const T f1 = T(rank(c1)) / tn;
+    const T dfdp = en_mul(en_sub(f1, f0), scale);
+    const double a = (double)en_sub(en_mul(T(2), f0), T(1));
+    const double d = en_sub(en_add(en_mul(a, acosdiff[icl]), en_mul(acoef[icl], (double)dfdp)), proddiff[icl]);
+    if (masked) {
+      const bool m = c1 > teps;  // efi.py:68
+      efi = en_add(efi, m ? d : 0.0);
+      efimax = en_add(efimax, m ? en_sub(-acosdiff[icl], proddiff[icl]) : 0.0);
+    } else {
+      efi = en_add(efi, d);
+    }
+    f0 = f1;
+  }
+  if (masked)
+    efi = efi / en_max(efimax, eps);
+  else
+    efi = en_mul(efi, 2.0 / 3.14159265358979323846);
+  return missing ? nan_v<double>() : efi;
+}
+
+// numpy.percentile(ens, q=perc, axis=0) with a Python int perc (method "linear"), as sot.py:91 calls it: the quantile
+// is perc / T(100), the virtual index (n - 1) * quantile, gamma its fractional part -- all in T, the dtype of ens.
+template <class T>
+struct Percentile {
+  unsigned lo, hi;
+  T gamma;
+};
+
+template <class T>
+inline Percentile<T> percentile_position(unsigned nens, int perc) {
+  Percentile<T> p;
+  const T q = T(perc) / T(100);
+  const T vi = en_mul(T(nens - 1), q);
+  if (vi >= T(nens - 1)) {  // numpy clips both neighbours to the last member and leaves -1 as "previous index"
+    p.lo = p.hi = nens - 1;
+    p.gamma = en_sub(vi, T(-1));
+  } else {
+    const T fl = std::floor(vi);
+    p.lo = (unsigned)fl;
+    p.hi = p.lo + 1;
+    p.gamma = en_sub(vi, fl);
+  }
+  return p;
+}
+
+// numpy's _lerp(a, b, t)
+template <class T>
+EKM_HD T en_lerp(T a, T b, T t) {
+  const T diff = en_sub(b, a);
+  if (t >= T(0.5)) return en_sub(b, en_mul(diff, en_sub(T(1), t)));
+  return en_add(a, en_mul(diff, t));
+}
+
+// sot.py:42-48
+template <class T>
+EKM_HD T sot_func_point(T qc_tail, T qc, T qf, T min_den, T lower, T upper) {
+  const T den = en_sub(qc_tail, qc);
+  T r = std::fabs(den) > min_den ? en_sub(qf, qc_tail) / den : nan_v<T>();
+  if (r < lower) r = lower;
+  if (r > upper) r = upper;
+  return r;
+}
+
+// sot.py:85-103 for one point whose members were zeroed below eps (when eps > 0) BEFORE they were sorted (sot.py:88)
+template <class T, class Sorted>
+EKM_HD T sot_point(T qc, T qc_tail, bool ens_nan, Sorted s, Percentile<T> pos, double eps) {
+  if (eps > 0.0 && qc < T(eps)) qc = T(0);  // sot.py:89
+  const T qf = ens_nan ? nan_v<T>() : en_lerp(s(pos.lo), s(pos.hi), pos.gamma);
+  return sot_func_point<T>(qc_tail, qc, qf, T(eps > 0.0 ? eps : 0.0), T(-10), T(10));
+}
+
+// ensemble.py:52-77 (Hersbach 2000).  The differences are formed in T, alpha and beta are float64 (xp.zeros), the sum
+// over i = 0..nens runs in order, starting from the i = 0 term.  p2[i] = (i/n)^2, q2[i] = (1 - i/n)^2: nens+1 values.
+template <class T, class Sorted>
+EKM_HD double crps_point(unsigned n, T y, Sorted s, const double* p2, const double* q2) {
+  double sum = 0.0;
+  T xm = s(0);
+  for (unsigned i = 0; i <= n; ++i) {
+    double alpha, beta;
+    if (i == 0) {
+      alpha = 0.0;
+      beta = en_max((double)en_sub(xm, y), 0.0);
+    } else if (i == n) {
+      alpha = en_max(-(double)en_sub(xm, y), 0.0);
+      beta = 0.0;
+    } else {
+      const T xi = s(i);
+      const double dxx = (double)en_sub(xi, xm);
+      alpha = en_min(dxx, en_max(-(double)en_sub(xm, y), 0.0));
+      beta = en_min(dxx, en_max((double)en_sub(xi, y), 0.0));
+      xm = xi;
+    }
+    const double term = en_add(en_mul(alpha, p2[i]), en_mul(beta, q2[i]));
+    sum = i == 0 ? term : en_add(sum, term);
+  }
+  return sum;
+}
+
+}  // namespace ekm

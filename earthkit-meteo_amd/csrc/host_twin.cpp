@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "ensemble_point.hpp"
 #include "interp_point.hpp"
 #include "ops.hpp"
 
@@ -139,3 +140,67 @@ EKM_HOST_HEIGHT(f64, double)
 EKM_HOST_INTERP(f32, float)
 EKM_HOST_INTERP(f64, double)
 #undef EKM_HOST_INTERP
+
+// ---- ensemble reductions: the per-point routines of ensemble.hip (ensemble_point.hpp) on the CPU, same arguments as
+// the ekm_efi_* / ekm_sot_* / ekm_sot_func_* / ekm_crps_from_ensemble_* entry points without dev / stream ----
+template <class T>
+static bool host_sort_members(const T* ens, unsigned nens, size_t npts, size_t p, std::vector<T>& col, bool zero_below, T teps) {
+  bool has_nan = false;
+  for (unsigned m = 0; m < nens; ++m) {
+    T x = ens[(size_t)m * npts + p];
+    if (zero_below && x < teps) x = T(0);
+    has_nan = has_nan || x != x;
+    ekm::ens_insert<T>(m, x, [&](unsigned j) { return col[j]; }, [&](unsigned j, T v) { col[j] = v; });
+  }
+  return has_nan;
+}
+
+#define EKM_HOST_ENSEMBLE(tag, T)                                                                                    \
+  extern "C" int ekm_host_efi_##tag(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts,         \
+                                    double eps, const double* acosdiff, const double* proddiff, const double* acoef, \
+                                    double* out) {                                                                   \
+    if (nclim < 1 || nens < 1) return -2;                                                                            \
+    std::vector<T> col(nens);                                                                                        \
+    for (size_t p = 0; p < npts; ++p) {                                                                              \
+      const bool has_nan = host_sort_members<T>(ens, nens, npts, p, col, false, T(0));                               \
+      out[p] = ekm::efi_point<T>(                                                                                    \
+          nclim, nens, has_nan, [&](unsigned i) { return clim[(size_t)i * npts + p]; },                              \
+          [&](unsigned j) { return col[j]; }, acosdiff, proddiff, acoef, eps);                                       \
+    }                                                                                                                \
+    return 0;                                                                                                        \
+  }                                                                                                                  \
+  extern "C" int ekm_host_sot_##tag(const T* qc, const T* qc_tail, const T* ens, unsigned nens, size_t npts,         \
+                                    int perc, double eps, T* out) {                                                  \
+    if (nens < 1 || perc < 2 || perc > 98 || perc == 50) return -2;                                                  \
+    std::vector<T> col(nens);                                                                                        \
+    const ekm::Percentile<T> pos = ekm::percentile_position<T>(nens, perc);                                          \
+    for (size_t p = 0; p < npts; ++p) {                                                                              \
+      const bool has_nan = host_sort_members<T>(ens, nens, npts, p, col, eps > 0.0, T(eps));                         \
+      out[p] = ekm::sot_point<T>(qc[p], qc_tail[p], has_nan, [&](unsigned j) { return col[j]; }, pos, eps);          \
+    }                                                                                                                \
+    return 0;                                                                                                        \
+  }                                                                                                                  \
+  extern "C" int ekm_host_sot_func_##tag(const T* qc_tail, const T* qc, const T* qf, size_t n, double eps,           \
+                                         double lower_bound, double upper_bound, T* out) {                           \
+    for (size_t p = 0; p < n; ++p)                                                                                   \
+      out[p] = ekm::sot_func_point<T>(qc_tail[p], qc[p], qf[p], T(eps > 0.0 ? eps : 0.0), T(lower_bound),            \
+                                      T(upper_bound));                                                               \
+    return 0;                                                                                                        \
+  }                                                                                                                  \
+  extern "C" int ekm_host_crps_from_ensemble_##tag(const T* x, const T* y, unsigned nens, size_t npts,               \
+                                                   const double* p2, const double* q2, double* out,                  \
+                                                   unsigned char* missing) {                                         \
+    if (nens < 1) return -2;                                                                                         \
+    std::vector<T> col(nens);                                                                                        \
+    for (size_t p = 0; p < npts; ++p) {                                                                              \
+      const bool has_nan = host_sort_members<T>(x, nens, npts, p, col, false, T(0));                                 \
+      const bool miss = has_nan || y[p] != y[p];                                                                     \
+      const double r = ekm::crps_point<T>(nens, y[p], [&](unsigned j) { return col[j]; }, p2, q2);                   \
+      out[p] = miss ? ekm::nan_v<double>() : r;                                                                      \
+      if (missing) missing[p] = miss ? 1 : 0;                                                                        \
+    }                                                                                                                \
+    return 0;                                                                                                        \
+  }
+EKM_HOST_ENSEMBLE(f32, float)
+EKM_HOST_ENSEMBLE(f64, double)
+#undef EKM_HOST_ENSEMBLE

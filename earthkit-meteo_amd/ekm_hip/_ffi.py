@@ -86,6 +86,11 @@ def _signatures():
         sig[f"ekm_height_from_geopotential_{tag}"] = ([i, vp, vp, vp, sz, u32, i, vp], i)
         sig[f"ekm_interpolate_hybrid_to_pressure_{tag}"] = (
             [i, vp, vp, vp, vp, vp, vp, i, u32, sz, u32, i, i, vp, vp, vp, vp, u32, vp], i)
+        dbl = C.c_double
+        sig[f"ekm_efi_{tag}"] = ([i, vp, vp, vp, u32, u32, sz, dbl, vp, vp, vp, vp], i)
+        sig[f"ekm_sot_{tag}"] = ([i, vp, vp, vp, vp, u32, sz, i, dbl, vp], i)
+        sig[f"ekm_sot_func_{tag}"] = ([i, vp, vp, vp, vp, sz, dbl, dbl, dbl, vp], i)
+        sig[f"ekm_crps_from_ensemble_{tag}"] = ([i, vp, vp, vp, u32, sz, vp, vp, vp, vp], i)
     for name, (ins, outs, ints, has_eps) in OPS.items():
         for tag, real in (("f32", C.c_float), ("f64", C.c_double)):
             args = [i, vp] + [C.POINTER(Operand)] * len(ins) + [i] * len(ints)

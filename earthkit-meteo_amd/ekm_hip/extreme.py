@@ -1,0 +1,121 @@
+"""`earthkit.meteo.extreme` on MI355X: Extreme Forecast Index and Shift of Tails of an ensemble against a model
+climate (reference extreme/array/efi.py, extreme/array/sot.py; kernels csrc/ensemble.hip).
+
+Same names, argument order, defaults and error conventions as the reference.  NumPy in -> NumPy out; `DeviceArray` in
+-> `DeviceArray` out; device tensors of another ROCm library are taken over through DLPack and handed back in that
+library's type.  Fields are member-major: `clim` [nclim, npoints], `ens` [nens, npoints]; at most 256 members in f32 and
+128 in f64 (more raises `EkmError`).
+
+The arithmetic runs in f32 when every array argument is f32 and in f64 otherwise (f64, mixed, integer).  In f32 and in
+f64 the results equal the reference's bit for bit.  Deviation: with mixed dtypes the reference's `efi` forms `frac` in
+`clim`'s dtype (so in f32 when only `clim` is f32) while this computes in f64; the two differ by the rounding of `frac`
+and `dFdp` to f32 (about 1e-8 absolute on the index, see tests/_ensemble_numpy.py::mixed_efi_bound).
+
+`cpf` (marked experimental in the reference, a stateful scan) and `sot_unsorted` (raises on every call in the
+reference) are not provided.
+"""
+import numpy as np
+
+from . import _ensemble as _e
+from .device import DeviceArray, current_stream
+from .vertical import _foreign_aware
+
+_F32 = np.dtype(np.float32)
+
+
+def efi_coefficients(nclim):
+    """(acosdiff, proddiff, acoef) of efi.py:54-60, computed with NumPy as the reference computes them: the kernel takes
+    them as tables and evaluates no acos."""
+    p = np.linspace(0.0, 1.0, nclim)
+    acosdiff = np.diff(np.acos(np.sqrt(p)))
+    proddiff = np.diff(np.sqrt(p * (1.0 - p)))
+    acoef = (1.0 - 2.0 * p[:-1]) * acosdiff + proddiff
+    return acosdiff, proddiff, acoef
+
+
+@_foreign_aware("clim", "ens")
+def efi(clim, ens, eps=-0.1):
+    """Extreme Forecast Index (efi.py:16-89).  clim: (nclim, npoints) per-point climatology, sorted or not; ens:
+    (nens, npoints).  Returns float64 (npoints) for f32 and f64 input, NaN where a column of clim or ens holds a NaN."""
+    clim, ens = _e.as_input(clim), _e.as_input(ens)
+    if len(clim.shape) != 2 or len(ens.shape) != 2:
+        raise ValueError(f"efi: clim and ens must be 2-D (nclim, npoints) and (nens, npoints), got {tuple(clim.shape)} and {tuple(ens.shape)}")
+    nclim, npts = (int(v) for v in clim.shape)
+    nens, npts_ens = (int(v) for v in ens.shape)
+    assert npts == npts_ens  # efi.py:45
+    eps = float(eps)
+    dtype = _e.arith_dtype(clim, ens)
+    device, stream, keep = _e.device_of(clim, ens), current_stream(), []
+    if nens < 1 or nclim < 1:
+        raise ValueError("efi: clim and ens need at least one row each")
+    _, tabs = _e.table("efi", nclim, device, lambda: efi_coefficients(nclim))
+    d_clim = _e.upload(clim, dtype, device, stream, keep)
+    d_ens = _e.upload(ens, dtype, device, stream, keep)
+    out = DeviceArray.empty((npts,), np.float64, device)
+    _e._ffi.check(getattr(_e.lib(), f"ekm_efi_{_e.tag_of(dtype)}")(
+        device, stream, d_clim.ptr, d_ens.ptr, nclim, nens, npts, eps, tabs[0].on(stream), tabs[1].on(stream),
+        tabs[2].on(stream), out.on(stream)))
+    return _e.finish(out, _e.on_device(clim, ens))
+
+
+def _points_shape(a, b, what):
+    if len(a.shape) < 1 or len(b.shape) < 1 or tuple(a.shape[1:]) != tuple(b.shape[1:]):
+        raise ValueError(f"{what}: the point dimensions differ: {tuple(a.shape)} against {tuple(b.shape)}")
+    return tuple(int(v) for v in a.shape[1:])
+
+
+@_foreign_aware("clim", "ens")
+def sot(clim, ens, perc, eps=-1e4):
+    """Shift of Tails (sot.py:51-103) from the 101 climate percentiles `clim` (101, ...) and the unsorted ensemble `ens`
+    (nens, ...); trailing dimensions are flattened to points.  `perc`: an int in [2, 98], not 50.  The result has the
+    points' shape, in the arithmetic dtype."""
+    clim, ens = _e.as_input(clim), _e.as_input(ens)
+    if not (isinstance(perc, int) or isinstance(perc, np.int64)) or (perc < 2 or perc > 98):
+        raise Exception("Percentile value should be and Integer between 2 and 98, is {}".format(perc))
+    if clim.shape[0] != 101:
+        raise Exception("Climatology array should contain 101 percentiles, it has {} values".format(tuple(clim.shape)))
+    if perc == 50:
+        raise Exception("Percentile value to be computed cannot be 50 for sot, has to be in the upper or lower half")
+    pts = _points_shape(clim, ens, "sot")
+    npts, nens, perc, eps = _e.npoints(pts), int(ens.shape[0]), int(perc), float(eps)
+    if nens < 1:
+        raise ValueError("sot: ens needs at least one member")
+    tail = 99 if perc > 50 else 1
+    dtype = _e.arith_dtype(clim, ens)
+    device, stream, keep = _e.device_of(clim, ens), current_stream(), []
+    if isinstance(clim, DeviceArray):
+        d_clim = _e.upload(clim, dtype, device, stream, keep)
+        row = npts * dtype.itemsize
+        p_qc, p_tail = d_clim.ptr + perc * row, d_clim.ptr + tail * row
+    else:  # only the two rows the result depends on travel
+        d_rows = _e.upload(np.stack([clim[perc].reshape(-1), clim[tail].reshape(-1)]), dtype, device, stream, keep)
+        p_qc, p_tail = d_rows.ptr, d_rows.ptr + npts * dtype.itemsize
+    d_ens = _e.upload(ens, dtype, device, stream, keep)
+    out = DeviceArray.empty(pts, dtype, device)
+    _e._ffi.check(getattr(_e.lib(), f"ekm_sot_{_e.tag_of(dtype)}")(
+        device, stream, p_qc, p_tail, d_ens.ptr, nens, npts, perc, eps, out.on(stream)))
+    return _e.finish(out, _e.on_device(clim, ens))
+
+
+@_foreign_aware("qc_tail", "qc", "qf")
+def sot_func(qc_tail, qc, qf, eps=-1e-4, lower_bound=-10, upper_bound=10):
+    """Shift of Tails from percentiles that are computed already (sot.py:13-48): NaN where |qc_tail - qc| does not
+    exceed max(eps, 0), clamped to [lower_bound, upper_bound].  NumPy arguments broadcast; DeviceArrays must agree in
+    shape."""
+    args = [_e.as_input(x) for x in (qc_tail, qc, qf)]
+    device_result = _e.on_device(*args)
+    if device_result:
+        shape = tuple(next(a.shape for a in args if isinstance(a, DeviceArray)))
+        if any(tuple(a.shape) != shape for a in args):
+            raise ValueError(f"sot_func: DeviceArray arguments must have one shape, got {[tuple(a.shape) for a in args]}")
+    else:
+        args = list(np.broadcast_arrays(*args))
+        shape = args[0].shape
+    dtype = _e.arith_dtype(*args)
+    device, stream, keep = _e.device_of(*args), current_stream(), []
+    d = [_e.upload(a, dtype, device, stream, keep) for a in args]
+    out = DeviceArray.empty(shape, dtype, device)
+    _e._ffi.check(getattr(_e.lib(), f"ekm_sot_func_{_e.tag_of(dtype)}")(
+        device, stream, d[0].ptr, d[1].ptr, d[2].ptr, _e.npoints(shape), float(eps), float(lower_bound),
+        float(upper_bound), out.on(stream)))
+    return _e.finish(out, device_result)

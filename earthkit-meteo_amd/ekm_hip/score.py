@@ -1,0 +1,70 @@
+"""`earthkit.meteo.score.crps_from_ensemble` on MI355X (reference score/array/ensemble.py; kernel csrc/ensemble.hip).
+
+Same name, argument order, default and error conventions as the reference.  NumPy in -> NumPy out; `DeviceArray` in ->
+`DeviceArray` out; device tensors of another ROCm library go through DLPack.  `x` is member-major (n_ens, ...), `y` has
+the points' shape; trailing dimensions are flattened to points.  At most 256 members in f32 and 128 in f64.  The
+differences are formed in f32 when x and y are both f32 and in f64 otherwise; the result is float64 and equals the
+reference's bit for bit.
+
+nan_policy: "propagate" leaves NaN at points where x or y holds a NaN.  "raise" and "omit" read the kernel's one-byte
+"missing" flags back to the host, so they wait for the device (and cannot be recorded into a graph); "omit" returns the
+1-D result of the remaining points, compacted on the host also for DeviceArray input (then uploaded again).
+"""
+import numpy as np
+
+from . import _ensemble as _e
+from .device import DeviceArray, _Allocation, current_stream
+from .vertical import _foreign_aware
+
+
+def crps_weights(n_ens):
+    """(p**2, (1 - p)**2) for p = arange(n_ens + 1) / n_ens (ensemble.py:76-77), as the reference computes them."""
+    p = np.arange(n_ens + 1) / float(n_ens)
+    return p**2, (1 - p) ** 2
+
+
+@_foreign_aware("x", "y")
+def crps_from_ensemble(x, y, nan_policy="propagate"):
+    """Continuous Ranked Probability Score of the ensemble x (n_ens, n_points) against y (n_points), Hersbach (2000)
+    (ensemble.py:13-82).  Returns float64 with y's shape ("omit": 1-D, the points without missing values)."""
+    if nan_policy not in ["raise", "propagate", "omit"]:
+        raise ValueError("Invalid argument: nan_policy must be 'raise', 'propagate', or 'omit'.")
+    x, y = _e.as_input(x), _e.as_input(y)
+    if len(x.shape) < 1 or tuple(x.shape[1:]) != tuple(y.shape):
+        raise ValueError(f"crps_from_ensemble: x {tuple(x.shape)} must be (n_ens,) + the shape of y {tuple(y.shape)}")
+    pts = tuple(int(v) for v in y.shape)
+    npts, nens = _e.npoints(pts), int(x.shape[0])
+    if nens < 1:
+        raise ValueError("crps_from_ensemble: x needs at least one member")
+    device_result = _e.on_device(x, y)
+    if nan_policy == "raise" and not device_result:
+        # the reference's test on the host input, before any GPU work (ensemble.py:44-47)
+        if bool(np.any(np.isnan(x))) or bool(np.any(np.isnan(y))):
+            raise ValueError(f"Missing values present in input and nan_policy={nan_policy}")
+    dtype = _e.arith_dtype(x, y)
+    device, stream, keep = _e.device_of(x, y), current_stream(), []
+    _, tabs = _e.table("crps", nens, device, lambda: crps_weights(nens))
+    d_x = _e.upload(x, dtype, device, stream, keep)
+    d_y = _e.upload(y, dtype, device, stream, keep)
+    out = DeviceArray.empty(pts, np.float64, device)
+    flags = None
+    if nan_policy != "propagate":
+        flags = _Allocation(max(npts, 16), device)
+        flags.touch(stream)
+    _e._ffi.check(getattr(_e.lib(), f"ekm_crps_from_ensemble_{_e.tag_of(dtype)}")(
+        device, stream, d_x.ptr, d_y.ptr, nens, npts, tabs[0].on(stream), tabs[1].on(stream), out.on(stream),
+        flags.ptr if flags is not None else None))
+    if flags is None:
+        return _e.finish(out, device_result)
+    missing = np.zeros(max(npts, 1), np.uint8)
+    lib = _e.lib()
+    _e._ffi.check(lib.ekm_d2h(device, missing.ctypes.data, flags.ptr, npts, stream))
+    _e._ffi.check(lib.ekm_stream_sync(device, stream))
+    flags.free()
+    missing = missing[:npts].astype(bool)
+    if nan_policy == "raise":
+        if missing.any():
+            raise ValueError(f"Missing values present in input and nan_policy={nan_policy}")
+        return _e.finish(out, device_result)
+    res = _e.finish(out, False).reshape(-1)[~missing]
+    return DeviceArray.from_host(res, device) if device_result else res

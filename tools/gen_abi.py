@@ -171,7 +171,9 @@ typedef struct ekm_operand {
  * other call (ekm_hip/_ffi.py does); a library older than version 5 does not export the function at all.
  *   5  (round 5) ekm_abi_version added.  Since round 3 (unnumbered "4"): ekm_copy_staged, ekm_host_memcpy,
  *      ekm_host_register, ekm_host_unregister removed; "table_tiles" default 8 -> 0 (= by op); field pointers must be
- *      aligned to their element size; at most 32 KiB (was 64) of staged level vectors per launch. */
+ *      aligned to their element size; at most 32 KiB (was 64) of staged level vectors per launch.
+ *      Added since, without a bump (an addition breaks no client): the vertical interpolation entry points; the ensemble
+ *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -361,6 +363,46 @@ EKM_API int ekm_interpolate_hybrid_to_pressure_f64(int dev, void* stream, const 
                                                    int descending, int mode, const double* aux_min_data,
                                                    const double* aux_min_coord, const double* aux_max_data,
                                                    const double* aux_max_coord, uint32_t aux_field_mask, double* out);
+
+/* ---- ensemble reductions: Extreme Forecast Index, Shift of Tails, CRPS ----
+ * One lane per grid point; fields are member-major: clim [nclim, npts], ens / x [nens, npts].  The point's ensemble is
+ * sorted in LDS: nens <= 256 (_f32) / 128 (_f64), more members return EKM_ERR_ARG.  Every operation is rounded once in
+ * the reference's order and the f64 sums run in its loop order: the results equal the reference's (NumPy) bit for bit.
+ * Like every compute entry point these only enqueue a kernel: nothing allocates, copies or waits on the host.
+ *
+ * efi: reference extreme/array/efi.py:34-89.  clim need not be sorted (the reference counts members <= clim[i]); its
+ * rows are streamed once, nclim >= 1 is unbounded.  acosdiff, proddiff, acoef: the nclim-1 float64 coefficients of
+ * efi.py:54-60 on the device, computed by the caller (ekm_hip.extreme does it with NumPy as the reference does; no
+ * acos is evaluated here).  eps > 0 selects the masked sum divided by max(efimax, eps), eps <= 0 the plain sum * 2/pi.
+ * out: float64 [npts] for both input dtypes; NaN where a column of clim or ens holds a NaN. */
+EKM_API int ekm_efi_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens,
+                        size_t npts, double eps, const double* acosdiff, const double* proddiff, const double* acoef,
+                        double* out);
+EKM_API int ekm_efi_f64(int dev, void* stream, const double* clim, const double* ens, uint32_t nclim, uint32_t nens,
+                        size_t npts, double eps, const double* acosdiff, const double* proddiff, const double* acoef,
+                        double* out);
+/* sot: reference extreme/array/sot.py:51-103.  qc = row `perc` of the climate, qc_tail = row 99 (perc > 50) or row 1
+ * (perc < 50): [npts] each, passed as row pointers.  perc in [2, 98], not 50.  The forecast percentile is
+ * numpy.percentile's linear method in the input dtype; with eps > 0 members and qc below eps count as 0.  out: [npts]
+ * in the input dtype. */
+EKM_API int ekm_sot_f32(int dev, void* stream, const float* qc, const float* qc_tail, const float* ens, uint32_t nens,
+                        size_t npts, int perc, double eps, float* out);
+EKM_API int ekm_sot_f64(int dev, void* stream, const double* qc, const double* qc_tail, const double* ens, uint32_t nens,
+                        size_t npts, int perc, double eps, double* out);
+/* sot_func: reference extreme/array/sot.py:13-48, elementwise over n points:
+ * |qc_tail - qc| > max(eps, 0) ? (qf - qc_tail) / (qc_tail - qc) : NaN, clamped to [lower_bound, upper_bound]. */
+EKM_API int ekm_sot_func_f32(int dev, void* stream, const float* qc_tail, const float* qc, const float* qf, size_t n,
+                             double eps, double lower_bound, double upper_bound, float* out);
+EKM_API int ekm_sot_func_f64(int dev, void* stream, const double* qc_tail, const double* qc, const double* qf, size_t n,
+                             double eps, double lower_bound, double upper_bound, double* out);
+/* crps_from_ensemble: reference score/array/ensemble.py:34-82.  x: [nens, npts], y: [npts]; p2[i] = (i/nens)^2 and
+ * q2[i] = (1 - i/nens)^2, i = 0..nens, float64 on the device (computed by the caller as the reference computes them).
+ * out: float64 [npts], NaN where x or y holds a NaN; missing (may be NULL): one byte per point, 1 exactly there -- the
+ * reference's isnan_mask, which the NaN of `out` cannot stand for (+-inf input gives NaN without being missing). */
+EKM_API int ekm_crps_from_ensemble_f32(int dev, void* stream, const float* x, const float* y, uint32_t nens, size_t npts,
+                                       const double* p2, const double* q2, double* out, uint8_t* missing);
+EKM_API int ekm_crps_from_ensemble_f64(int dev, void* stream, const double* x, const double* y, uint32_t nens,
+                                       size_t npts, const double* p2, const double* q2, double* out, uint8_t* missing);
 
 /* ---- thermo entry points ----
  * Argument order: dev, stream, inputs..., enum parameters..., [eps], outputs..., n. */
