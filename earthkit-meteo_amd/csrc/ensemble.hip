@@ -1,5 +1,6 @@
-// Ensemble reductions on gfx950: Extreme Forecast Index, Shift of Tails and CRPS.
-// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82.
+// Ensemble reductions on gfx950: Extreme Forecast Index, Shift of Tails, CRPS and per-point quantiles.
+// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82,
+// stats/array/quantiles.py:18-84.
 //
 // One kernel family: one lane per grid point, one wave (64 lanes) per workgroup.  The fields are member-major,
 // ens [nens, npts] and clim [nclim, npts], so a wave reads a member row as one coalesced run.  The lane's ensemble is
@@ -10,6 +11,11 @@
 //          Traffic: (nclim + nens) elements read, 8 B written per point.
 //  * sot:  the percentile of the sorted ensemble (numpy's lerp) against two climate rows.
 //  * crps: Hersbach's alpha/beta walk over the sorted ensemble; optional 1-B "missing" flag per point.
+//  * quantiles: nq levels of the sorted column from host-computed position records, written level-major
+//          (out[k * npts + p]: one coalesced run per level and wave).  The sample axis need not lead: the array is
+//          [outer, m, inner] and point p = o * inner + i reads sample j at (o * m + j) * inner + i.  With the sample axis
+//          last (inner == 1) every lane reads its own contiguous column; staging the wave's run through LDS first was
+//          measured slower and is not kept (profiles/HISTORY.md).
 // LDS: nens * 64 * sizeof(T) <= 64 KiB per workgroup: nens <= 256 (fp32) / 128 (fp64); beyond that the entry points
 // return EKM_ERR_ARG.  The per-point arithmetic is ensemble_point.hpp, shared with the host twin.
 #include <hip/hip_runtime.h>
@@ -26,11 +32,11 @@ constexpr int kEnsLanes = 64;                   // one wave per workgroup
 constexpr size_t kEnsLdsBytes = 64 * 1024;      // the sorted ensembles of a workgroup
 constexpr int kEnsBatch = 8;                    // member rows in flight per lane while sorting
 
-// Streams the nens member rows of point p into the lane's LDS column, sorted ascending; returns "a member is NaN".
-// zero_below: sot.py:88 (members below eps become 0 before the percentile).
+// Streams the nens members of one point (member j at base[j * stride]) into the lane's LDS column, sorted ascending;
+// returns "a member is NaN".  zero_below: sot.py:88 (members below eps become 0 before the percentile).
 template <class T>
-__device__ __forceinline__ bool sort_members(const T* __restrict__ ens, unsigned nens, unsigned long long npts,
-                                             unsigned long long p, T* col, bool zero_below, T teps) {
+__device__ __forceinline__ bool sort_members(const T* __restrict__ base, unsigned long long stride, unsigned nens, T* col,
+                                             bool zero_below, T teps) {
   auto get = [&](unsigned j) -> T { return col[j * kEnsLanes]; };
   auto set = [&](unsigned j, T v) { col[j * kEnsLanes] = v; };
   bool has_nan = false;
@@ -38,7 +44,7 @@ __device__ __forceinline__ bool sort_members(const T* __restrict__ ens, unsigned
     T v[kEnsBatch];
 #pragma unroll
     for (int b = 0; b < kEnsBatch; ++b)
-      if (m0 + b < nens) v[b] = ens[(unsigned long long)(m0 + b) * npts + p];
+      if (m0 + b < nens) v[b] = base[(unsigned long long)(m0 + b) * stride];
 #pragma unroll
     for (int b = 0; b < kEnsBatch; ++b)
       if (m0 + b < nens) {
@@ -60,7 +66,7 @@ __global__ __launch_bounds__(kEnsLanes) void efi_points(const T* __restrict__ cl
   const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
   if (p >= npts) return;
   T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
-  const bool has_nan = sort_members<T>(ens, nens, npts, p, col, false, T(0));
+  const bool has_nan = sort_members<T>(ens + p, npts, nens, col, false, T(0));
   out[p] = efi_point<T>(
       nclim, nens, has_nan, [&](unsigned i) -> T { return clim[(unsigned long long)i * npts + p]; },
       [&](unsigned j) -> T { return col[j * kEnsLanes]; }, acosdiff, proddiff, acoef, eps);
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(kEnsLanes) void sot_points(const T* __restrict__ qc
   const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
   if (p >= npts) return;
   T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
-  const bool has_nan = sort_members<T>(ens, nens, npts, p, col, eps > 0.0, T(eps));
+  const bool has_nan = sort_members<T>(ens + p, npts, nens, col, eps > 0.0, T(eps));
   out[p] = sot_point<T>(qc[p], qc_tail[p], has_nan, [&](unsigned j) -> T { return col[j * kEnsLanes]; }, pos, eps);
 }
 
@@ -86,12 +92,31 @@ __global__ __launch_bounds__(kEnsLanes) void crps_points(const T* __restrict__ x
   const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
   if (p >= npts) return;
   T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
-  const bool has_nan = sort_members<T>(x, nens, npts, p, col, false, T(0));
+  const bool has_nan = sort_members<T>(x + p, npts, nens, col, false, T(0));
   const T yp = y[p];
   const bool miss = has_nan || yp != yp;  // ensemble.py:44
   const double r = crps_point<T>(nens, yp, [&](unsigned j) -> T { return col[j * kEnsLanes]; }, p2, q2);
   out[p] = miss ? nan_v<double>() : r;
   if (missing) missing[p] = miss ? 1 : 0;
+}
+
+// quantiles.py:60-84.  arr: [outer, m, inner]; lo, hi, w: the nq position records; out: [nq, npts] in Out.
+static_assert(kQuantileSort == EKM_QUANTILE_SORT && kQuantileLerp == EKM_QUANTILE_LERP, "ensemble_point.hpp and the header disagree");
+
+template <class T, class Out>
+__global__ __launch_bounds__(kEnsLanes) void quantile_points(const T* __restrict__ arr, unsigned m,
+                                                             unsigned long long inner, unsigned long long npts,
+                                                             const double* __restrict__ lo, const double* __restrict__ hi,
+                                                             const double* __restrict__ w, unsigned nq, int mode,
+                                                             Out* __restrict__ out) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
+  if (p >= npts) return;
+  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
+  const unsigned long long o = p / inner, i = p - o * inner;
+  const bool has_nan = sort_members<T>(arr + o * m * inner + i, inner, m, col, false, T(0));
+  auto s = [&](unsigned k) -> T { return col[k * kEnsLanes]; };
+  for (unsigned k = 0; k < nq; ++k)
+    out[(unsigned long long)k * npts + p] = quantile_point<T, Out>(has_nan, s, (unsigned)lo[k], (unsigned)hi[k], w[k], mode);
 }
 
 template <class T>
@@ -192,9 +217,44 @@ static int launch_crps(int dev, void* stream, const T* x, const T* y, uint32_t n
   return ens_launched("crps_from_ensemble");
 }
 
+template <class T, class Out>
+static int launch_quantiles(int dev, void* stream, const T* arr, size_t outer, uint32_t m, size_t inner, const double* lo,
+                            const double* hi, const double* w, uint32_t nq, int mode, Out* out) {
+  if (outer == 0 || inner == 0 || nq == 0) return EKM_OK;
+  if (mode != EKM_QUANTILE_SORT && mode != EKM_QUANTILE_LERP)
+    return set_error(EKM_ERR_ENUM, "quantiles: mode=%d is not EKM_QUANTILE_SORT or EKM_QUANTILE_LERP", mode);
+  if (mode == EKM_QUANTILE_SORT && sizeof(Out) != sizeof(double))
+    return set_error(EKM_ERR_ARG, "quantiles: EKM_QUANTILE_SORT gives float64 (use ekm_quantiles_f32_f64 for float input)");
+  if (inner > ~(size_t)0 / outer) return set_error(EKM_ERR_ARG, "quantiles: too many points");
+  const size_t npts = outer * inner;
+  if (!lo || !hi || !w) return set_error(EKM_ERR_ARG, "quantiles: null position table");
+  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(Out))
+    return set_error(EKM_ERR_ARG, "quantiles: out is null or not aligned to its element size (%d B)", (int)sizeof(Out));
+  unsigned grid;
+  size_t lds;
+  int rc = ens_prepare<T>(dev, "quantiles", npts, m, {arr}, &grid, &lds);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL((quantile_points<T, Out>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), arr, m,
+                     (unsigned long long)inner, (unsigned long long)npts, lo, hi, w, nq, mode, out);
+  return ens_launched("quantiles");
+}
+
 }  // namespace ekm
 
 extern "C" {
+
+int ekm_quantiles_f32(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner, const double* lo,
+                      const double* hi, const double* w, uint32_t nq, int mode, float* out) {
+  return ekm::launch_quantiles<float, float>(dev, stream, arr, outer, m, inner, lo, hi, w, nq, mode, out);
+}
+int ekm_quantiles_f64(int dev, void* stream, const double* arr, size_t outer, uint32_t m, size_t inner, const double* lo,
+                      const double* hi, const double* w, uint32_t nq, int mode, double* out) {
+  return ekm::launch_quantiles<double, double>(dev, stream, arr, outer, m, inner, lo, hi, w, nq, mode, out);
+}
+int ekm_quantiles_f32_f64(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner, const double* lo,
+                          const double* hi, const double* w, uint32_t nq, int mode, double* out) {
+  return ekm::launch_quantiles<float, double>(dev, stream, arr, outer, m, inner, lo, hi, w, nq, mode, out);
+}
 
 int ekm_efi_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens, size_t npts,
                 double eps, const double* acosdiff, const double* proddiff, const double* acoef, double* out) {

@@ -1,9 +1,10 @@
 // Reductions over the member axis of one grid point: Extreme Forecast Index, Shift of Tails and CRPS of an ensemble
 // against a model climate or an analysis.  One statement of the arithmetic for the gfx950 kernels (ensemble.hip) and
 // the host test twin (host_twin.cpp).
-// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82.
+// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82,
+// stats/array/quantiles.py:18-84.
 //
-// All three work on the point's ensemble SORTED ascending; `s(j)` below reads sorted member j.  The results are held to
+// All of them work on the point's ensemble SORTED ascending; `s(j)` below reads sorted member j.  The results are held to
 // the reference bit for bit, so every operation is rounded once in the reference's order: nothing is contracted into
 // an fma (en_* below; the host twin is built with -ffp-contract=off), divisions are IEEE divisions, and the f64 sums
 // run sequentially in the reference's loop order.
@@ -146,6 +147,27 @@ EKM_HD T sot_point(T qc, T qc_tail, bool ens_nan, Sorted s, Percentile<T> pos, d
   if (eps > 0.0 && qc < T(eps)) qc = T(0);  // sot.py:89
   const T qf = ens_nan ? nan_v<T>() : en_lerp(s(pos.lo), s(pos.hi), pos.gamma);
   return sot_func_point<T>(qc_tail, qc, qf, T(eps > 0.0 ? eps : 0.0), T(-10), T(10));
+}
+
+// quantiles.py:60-84: one quantile level of one point.  The position record (lo, hi, w) of the level is computed by the
+// host exactly as the reference (method "sort") or numpy.quantile (methods "numpy_bulk", "numpy") computes it; nothing is
+// floored here.  `mode` is EKM_QUANTILE_SORT / EKM_QUANTILE_LERP of include/ekm_thermo.h:
+constexpr int kQuantileSort = 0, kQuantileLerp = 1;
+//  * EKM_QUANTILE_SORT (quantiles.py:76-83): s(lo) * (1 - w) + s(hi) * w with both products and the sum rounded once in
+//    float64 (a NumPy float64 scalar promotes an f32 array).  No shortcut for w == 0: an infinite s(hi) gives NaN there,
+//    as in the reference.
+//  * EKM_QUANTILE_LERP (numpy's _lerp as numpy.quantile calls it): the difference s(hi) - s(lo) is formed in T, the
+//    dtype of the data, then it and both members are promoted to Out, the dtype of gamma (float64 for "numpy_bulk", T for
+//    "numpy"); for T == Out this is en_lerp.
+template <class T, class Out, class Sorted>
+EKM_HD Out quantile_point(bool col_nan, Sorted s, unsigned lo, unsigned hi, double w, int mode) {
+  if (col_nan) return nan_v<Out>();
+  const T a = s(lo), b = s(hi);
+  if (mode == kQuantileSort)
+    return Out(en_add(en_mul((double)a, en_sub(1.0, w)), en_mul((double)b, w)));
+  const Out t = Out(w), diff = Out(en_sub(b, a));
+  if (t >= Out(0.5)) return en_sub(Out(b), en_mul(diff, en_sub(Out(1), t)));
+  return en_add(Out(a), en_mul(diff, t));
 }
 
 // ensemble.py:52-77 (Hersbach 2000).  The differences are formed in T, alpha and beta are float64 (xp.zeros), the sum

@@ -204,3 +204,31 @@ static bool host_sort_members(const T* ens, unsigned nens, size_t npts, size_t p
 EKM_HOST_ENSEMBLE(f32, float)
 EKM_HOST_ENSEMBLE(f64, double)
 #undef EKM_HOST_ENSEMBLE
+
+// ---- quantiles: quantile_point of ensemble_point.hpp on the CPU, same arguments as ekm_quantiles_* without dev / stream ----
+template <class T, class Out>
+static int host_quantiles(const T* arr, size_t outer, unsigned m, size_t inner, const double* lo, const double* hi,
+                          const double* w, unsigned nq, int mode, Out* out) {
+  if (outer == 0 || inner == 0 || nq == 0) return 0;
+  if (mode != ekm::kQuantileSort && mode != ekm::kQuantileLerp) return -3;
+  if (m < 1 || (mode == ekm::kQuantileSort && sizeof(Out) != sizeof(double))) return -2;
+  const size_t npts = outer * inner;
+  std::vector<T> col(m);
+  for (size_t p = 0; p < npts; ++p) {
+    const size_t o = p / inner, i = p - o * inner;
+    const bool has_nan = host_sort_members<T>(arr + o * m * inner, m, inner, i, col, false, T(0));
+    for (unsigned k = 0; k < nq; ++k)
+      out[(size_t)k * npts + p] = ekm::quantile_point<T, Out>(has_nan, [&](unsigned j) { return col[j]; }, (unsigned)lo[k],
+                                                             (unsigned)hi[k], w[k], mode);
+  }
+  return 0;
+}
+#define EKM_HOST_QUANTILES(tag, T, Out)                                                                              \
+  extern "C" int ekm_host_quantiles_##tag(const T* arr, size_t outer, unsigned m, size_t inner, const double* lo,    \
+                                          const double* hi, const double* w, unsigned nq, int mode, Out* out) {      \
+    return host_quantiles<T, Out>(arr, outer, m, inner, lo, hi, w, nq, mode, out);                                   \
+  }
+EKM_HOST_QUANTILES(f32, float, float)
+EKM_HOST_QUANTILES(f64, double, double)
+EKM_HOST_QUANTILES(f32_f64, float, double)
+#undef EKM_HOST_QUANTILES

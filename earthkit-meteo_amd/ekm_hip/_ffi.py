@@ -19,6 +19,7 @@ PHASE = {"mixed": 0, "water": 1, "ice": 2}
 EPT_METHOD = {"ifs": 0, "bolton35": 1, "bolton39": 2}
 T_METHOD = {"bisect": 0, "newton": 1, "direct": 2}
 LCL_METHOD = {"davies": 0, "bolton": 1}
+QUANTILE_SORT, QUANTILE_LERP = 0, 1
 
 
 class EkmError(RuntimeError):
@@ -91,6 +92,8 @@ def _signatures():
         sig[f"ekm_sot_{tag}"] = ([i, vp, vp, vp, vp, u32, sz, i, dbl, vp], i)
         sig[f"ekm_sot_func_{tag}"] = ([i, vp, vp, vp, vp, sz, dbl, dbl, dbl, vp], i)
         sig[f"ekm_crps_from_ensemble_{tag}"] = ([i, vp, vp, vp, u32, sz, vp, vp, vp, vp], i)
+    for tag in ("f32", "f64", "f32_f64"):
+        sig[f"ekm_quantiles_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp, vp, u32, i, vp], i)
     for name, (ins, outs, ints, has_eps) in OPS.items():
         for tag, real in (("f32", C.c_float), ("f64", C.c_double)):
             args = [i, vp] + [C.POINTER(Operand)] * len(ins) + [i] * len(ints)

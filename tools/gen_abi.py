@@ -173,7 +173,7 @@ typedef struct ekm_operand {
  *      ekm_host_register, ekm_host_unregister removed; "table_tiles" default 8 -> 0 (= by op); field pointers must be
  *      aligned to their element size; at most 32 KiB (was 64) of staged level vectors per launch.
  *      Added since, without a bump (an addition breaks no client): the vertical interpolation entry points; the ensemble
- *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*. */
+ *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*; the per-point quantiles ekm_quantiles_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -365,7 +365,7 @@ EKM_API int ekm_interpolate_hybrid_to_pressure_f64(int dev, void* stream, const 
                                                    const double* aux_max_coord, uint32_t aux_field_mask, double* out);
 
 /* ---- ensemble reductions: Extreme Forecast Index, Shift of Tails, CRPS ----
- * One lane per grid point; fields are member-major: clim [nclim, npts], ens / x [nens, npts].  The point's ensemble is
+ * One lane per grid point; fields are member-major: clim [nclim, npts], ens / x [nens, npts] (quantiles: any axis).  The point's ensemble is
  * sorted in LDS: nens <= 256 (_f32) / 128 (_f64), more members return EKM_ERR_ARG.  Every operation is rounded once in
  * the reference's order and the f64 sums run in its loop order: the results equal the reference's (NumPy) bit for bit.
  * Like every compute entry point these only enqueue a kernel: nothing allocates, copies or waits on the host.
@@ -403,6 +403,26 @@ EKM_API int ekm_crps_from_ensemble_f32(int dev, void* stream, const float* x, co
                                        const double* p2, const double* q2, double* out, uint8_t* missing);
 EKM_API int ekm_crps_from_ensemble_f64(int dev, void* stream, const double* x, const double* y, uint32_t nens,
                                        size_t npts, const double* p2, const double* q2, double* out, uint8_t* missing);
+/* quantiles: reference stats/array/quantiles.py:18-84 (iter_quantiles), all levels of a call in one launch.
+ * arr: [outer, m, inner] contiguous, the m samples of point p = o * inner + i at (o * m + j) * inner + i, so the sample
+ * axis may be any axis; m <= 256 (f32 data) / 128 (f64 data), more samples return EKM_ERR_ARG.
+ * lo, hi, w: the nq position records on the device as float64 vectors, computed by the caller exactly as the reference
+ * and numpy.quantile compute them (ekm_hip.stats.quantile_positions; no floor is evaluated here): lo and hi are the two
+ * neighbours in the sorted column (whole numbers < m), w the weight.
+ * mode: EKM_QUANTILE_SORT, quantiles.py:75-83: s[lo] * (1 - w) + s[hi] * w, each product and the sum rounded once in
+ *   float64 (f64 output only: _f64 and _f32_f64); EKM_QUANTILE_LERP, quantiles.py:60-73: numpy.quantile's linear method,
+ *   the difference s[hi] - s[lo] in the data's type, then numpy's _lerp in the output type with w as gamma.
+ * out: [nq, outer * inner], level-major, float for _f32, double for _f64 and _f32_f64 (f32 data, f64 result: what the
+ * reference returns for "sort" and "numpy_bulk").  A column that holds a NaN gives NaN at every level.
+ * outer * inner == 0 or nq == 0 returns EKM_OK without a launch. */
+#define EKM_QUANTILE_SORT 0
+#define EKM_QUANTILE_LERP 1
+EKM_API int ekm_quantiles_f32(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
+                              const double* lo, const double* hi, const double* w, uint32_t nq, int mode, float* out);
+EKM_API int ekm_quantiles_f64(int dev, void* stream, const double* arr, size_t outer, uint32_t m, size_t inner,
+                              const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
+EKM_API int ekm_quantiles_f32_f64(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
+                                  const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
 
 /* ---- thermo entry points ----
  * Argument order: dev, stream, inputs..., enum parameters..., [eps], outputs..., n. */
