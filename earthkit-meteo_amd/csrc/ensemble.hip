@@ -1,6 +1,7 @@
-// Ensemble reductions on gfx950: Extreme Forecast Index, Shift of Tails, CRPS and per-point quantiles.
-// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82,
-// stats/array/quantiles.py:18-84.
+// Ensemble reductions on gfx950: Extreme Forecast Index, Shift of Tails, Crossing Point Forecast, CRPS and per-point
+// quantiles.
+// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, extreme/array/cpf.py:13-155,
+// score/array/ensemble.py:34-82, stats/array/quantiles.py:18-84.
 //
 // One kernel family: one lane per grid point, one wave (64 lanes) per workgroup.  The fields are member-major,
 // ens [nens, npts] and clim [nclim, npts], so a wave reads a member row as one coalesced run.  The lane's ensemble is
@@ -16,7 +17,13 @@
 //          [outer, m, inner] and point p = o * inner + i reads sample j at (o * m + j) * inner + i.  With the sample axis
 //          last (inner == 1) every lane reads its own contiguous column; staging the wave's run through LDS first was
 //          measured slower and is not kept (profiles/HISTORY.md).
-// LDS: nens * 64 * sizeof(T) <= 64 KiB per workgroup: nens <= 256 (fp32) / 128 (fp64); beyond that the entry points
+//  * cpf:  the crossing-point scan of the sorted ensemble against the interior climate rows, `symmetric` included, in one
+//          launch.  The ensemble column always goes to LDS (sorted NaN-last, or copied as given): the scan re-reads
+//          members for every row.  The climate goes to LDS only when it has to be sorted; as given it streams from
+//          global memory (rows icl, icl-1 and the top row are all that is read).  The LDS is a static array in one of
+//          four sizes (20 / 40 / 80 / 160 KiB: 8 / 4 / 2 / 1 workgroups per CU), chosen by the rows the call needs, so
+//          101 x 51 with both sorts runs in f32 (38 KiB) and in f64 (76 KiB); beyond 160 KiB: EKM_ERR_ARG.
+// LDS (all but cpf): nens * 64 * sizeof(T) <= 64 KiB per workgroup: nens <= 256 (fp32) / 128 (fp64); beyond that the entry points
 // return EKM_ERR_ARG.  The per-point arithmetic is ensemble_point.hpp, shared with the host twin.
 #include <hip/hip_runtime.h>
 
@@ -119,6 +126,57 @@ __global__ __launch_bounds__(kEnsLanes) void quantile_points(const T* __restrict
     out[(unsigned long long)k * npts + p] = quantile_point<T, Out>(has_nan, s, (unsigned)lo[k], (unsigned)hi[k], w[k], mode);
 }
 
+// Streams the `rows` values of one point (row j at base[j * stride]) into the lane's LDS column: sorted as numpy.sort
+// orders them (NaN last), or as given.
+template <class T>
+__device__ __forceinline__ void stage_column(const T* __restrict__ base, unsigned long long stride, unsigned rows, T* col,
+                                             bool sort) {
+  auto get = [&](unsigned j) -> T { return col[j * kEnsLanes]; };
+  auto set = [&](unsigned j, T v) { col[j * kEnsLanes] = v; };
+  for (unsigned m0 = 0; m0 < rows; m0 += kEnsBatch) {
+    T v[kEnsBatch];
+#pragma unroll
+    for (int b = 0; b < kEnsBatch; ++b)
+      if (m0 + b < rows) v[b] = base[(unsigned long long)(m0 + b) * stride];
+#pragma unroll
+    for (int b = 0; b < kEnsBatch; ++b)
+      if (m0 + b < rows) {
+        if (sort)
+          ens_insert_nan_last<T>(m0 + b, v[b], get, set);
+        else
+          set(m0 + b, v[b]);
+      }
+  }
+}
+
+// cpf.py:13-155.  KIB: the static LDS of the workgroup; rows [0, nens) hold the ensemble column, rows [nens, nens+nclim)
+// the sorted climate column when sort_clim.
+constexpr unsigned kCpfSortClim = 1, kCpfSortEns = 2, kCpfFromZero = 4, kCpfSymmetric = 8, kCpfEpsilon = 16;
+constexpr size_t kCpfLdsMaxBytes = 160 * 1024;  // the LDS of a gfx950 workgroup
+
+template <class T, int KIB>
+__global__ __launch_bounds__(kEnsLanes) void cpf_points(const T* __restrict__ clim, const T* __restrict__ ens,
+                                                        unsigned nclim, unsigned nens, unsigned long long npts,
+                                                        unsigned flags, T epsilon, float* __restrict__ out) {
+  __shared__ T lds[(size_t)KIB * 1024 / sizeof(T)];
+  const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
+  if (p >= npts) return;
+  T* ecol = lds + threadIdx.x;
+  T* ccol = ecol + (size_t)nens * kEnsLanes;
+  stage_column<T>(ens + p, npts, nens, ecol, (flags & kCpfSortEns) != 0);
+  auto member = [&](unsigned j) -> T { return ecol[j * kEnsLanes]; };
+  const bool from_zero = (flags & kCpfFromZero) != 0, symmetric = (flags & kCpfSymmetric) != 0,
+             use_eps = (flags & kCpfEpsilon) != 0;
+  if (flags & kCpfSortClim) {
+    stage_column<T>(clim + p, npts, nclim, ccol, true);
+    out[p] = cpf_value<T>(nclim, nens, from_zero, symmetric, use_eps, epsilon,
+                          [&](unsigned i) -> T { return ccol[i * kEnsLanes]; }, member);
+  } else {
+    out[p] = cpf_value<T>(nclim, nens, from_zero, symmetric, use_eps, epsilon,
+                          [&](unsigned i) -> T { return clim[(unsigned long long)i * npts + p]; }, member);
+  }
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void sot_func_points(const T* __restrict__ qc_tail, const T* __restrict__ qc,
                                                        const T* __restrict__ qf, unsigned long long n, T min_den, T lower,
@@ -201,6 +259,48 @@ static int launch_sot_func(int dev, void* stream, const T* qc_tail, const T* qc,
   return ens_launched("sot_func");
 }
 
+template <class T, int KIB>
+static void launch_cpf_bucket(unsigned grid, void* stream, const T* clim, const T* ens, uint32_t nclim, uint32_t nens,
+                              size_t npts, unsigned flags, double epsilon, float* out) {
+  hipLaunchKernelGGL((cpf_points<T, KIB>), dim3(grid), dim3(kEnsLanes), 0, static_cast<hipStream_t>(stream), clim, ens, nclim,
+                     nens, (unsigned long long)npts, flags, T(epsilon), out);
+}
+
+template <class T>
+static int launch_cpf(int dev, void* stream, const T* clim, const T* ens, uint32_t nclim, uint32_t nens, size_t npts,
+                      int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon, double epsilon,
+                      float* out) {
+  if (npts == 0) return EKM_OK;
+  if (nclim < 1 || nens < 1) return set_error(EKM_ERR_ARG, "cpf: at least one climate row and one member are required");
+  const size_t rows = (size_t)nens + (sort_clim ? (size_t)nclim : 0);
+  const size_t lds = rows * kEnsLanes * sizeof(T);
+  if (lds > kCpfLdsMaxBytes)
+    return set_error(EKM_ERR_ARG, "cpf: %u members%s need %zu B of LDS per workgroup (max %zu: %zu rows)", nens,
+                     sort_clim ? " and the climate rows to sort" : "", lds, kCpfLdsMaxBytes,
+                     kCpfLdsMaxBytes / (kEnsLanes * sizeof(T)));
+  for (const void* ptr : {(const void*)clim, (const void*)ens}) {
+    if (!ptr) return set_error(EKM_ERR_ARG, "cpf: null pointer");
+    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(T))
+      return set_error(EKM_ERR_ARG, "cpf: a pointer is not aligned to its element size (%d B)", (int)sizeof(T));
+  }
+  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(float)) return set_error(EKM_ERR_ARG, "cpf: out is null or not 4-B aligned");
+  const unsigned long long g = ((unsigned long long)npts + kEnsLanes - 1) / kEnsLanes;
+  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "cpf: too many points");
+  int rc = use_device(dev);
+  if (rc != EKM_OK) return rc;
+  const unsigned flags = (sort_clim ? kCpfSortClim : 0) | (sort_ens ? kCpfSortEns : 0) | (from_zero ? kCpfFromZero : 0) |
+                         (symmetric ? kCpfSymmetric : 0) | (use_epsilon && !symmetric ? kCpfEpsilon : 0);
+  if (lds <= 20 * 1024)
+    launch_cpf_bucket<T, 20>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+  else if (lds <= 40 * 1024)
+    launch_cpf_bucket<T, 40>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+  else if (lds <= 80 * 1024)
+    launch_cpf_bucket<T, 80>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+  else
+    launch_cpf_bucket<T, 160>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+  return ens_launched("cpf");
+}
+
 template <class T>
 static int launch_crps(int dev, void* stream, const T* x, const T* y, uint32_t nens, size_t npts, const double* p2,
                        const double* q2, double* out, uint8_t* missing) {
@@ -281,6 +381,17 @@ int ekm_sot_func_f32(int dev, void* stream, const float* qc_tail, const float* q
 int ekm_sot_func_f64(int dev, void* stream, const double* qc_tail, const double* qc, const double* qf, size_t n, double eps,
                      double lower_bound, double upper_bound, double* out) {
   return ekm::launch_sot_func<double>(dev, stream, qc_tail, qc, qf, n, eps, lower_bound, upper_bound, out);
+}
+
+int ekm_cpf_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens, size_t npts,
+                int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon, double epsilon, float* out) {
+  return ekm::launch_cpf<float>(dev, stream, clim, ens, nclim, nens, npts, sort_clim, sort_ens, from_zero, symmetric,
+                                use_epsilon, epsilon, out);
+}
+int ekm_cpf_f64(int dev, void* stream, const double* clim, const double* ens, uint32_t nclim, uint32_t nens, size_t npts,
+                int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon, double epsilon, float* out) {
+  return ekm::launch_cpf<double>(dev, stream, clim, ens, nclim, nens, npts, sort_clim, sort_ens, from_zero, symmetric,
+                                 use_epsilon, epsilon, out);
 }
 
 int ekm_crps_from_ensemble_f32(int dev, void* stream, const float* x, const float* y, uint32_t nens, size_t npts,

@@ -1,8 +1,8 @@
 // Reductions over the member axis of one grid point: Extreme Forecast Index, Shift of Tails and CRPS of an ensemble
 // against a model climate or an analysis.  One statement of the arithmetic for the gfx950 kernels (ensemble.hip) and
 // the host test twin (host_twin.cpp).
-// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, score/array/ensemble.py:34-82,
-// stats/array/quantiles.py:18-84.
+// Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, extreme/array/cpf.py:13-155,
+// score/array/ensemble.py:34-82, stats/array/quantiles.py:18-84.
 //
 // All of them work on the point's ensemble SORTED ascending; `s(j)` below reads sorted member j.  The results are held to
 // the reference bit for bit, so every operation is rounded once in the reference's order: nothing is contracted into
@@ -50,6 +50,21 @@ EKM_HD void ens_insert(unsigned k, T v, Get get, Set set) {
   while (j > 0) {
     const T u = get(j - 1);
     if (!(u > v)) break;
+    set(j, u);
+    --j;
+  }
+  set(j, v);
+}
+
+// Member v goes into the sorted run s[0..k) as numpy.sort orders it: a NaN above every number (cpf.py:140-143 sorts and
+// then compares as usual, so the place of a NaN is read).
+template <class T, class Get, class Set>
+EKM_HD void ens_insert_nan_last(unsigned k, T v, Get get, Set set) {
+  const bool v_nan = v != v;
+  unsigned j = k;
+  while (j > 0) {
+    const T u = get(j - 1);
+    if (!(u > v || (u != u && !v_nan))) break;
     set(j, u);
     --j;
   }
@@ -147,6 +162,83 @@ EKM_HD T sot_point(T qc, T qc_tail, bool ens_nan, Sorted s, Percentile<T> pos, d
   if (eps > 0.0 && qc < T(eps)) qc = T(0);  // sot.py:89
   const T qf = ens_nan ? nan_v<T>() : en_lerp(s(pos.lo), s(pos.hi), pos.gamma);
   return sot_func_point<T>(qc_tail, qc, qf, T(eps > 0.0 ? eps : 0.0), T(-10), T(10));
+}
+
+// cpf.py:13-91 for one point: the Crossing Point Forecast of the column ens(0..nens) against the climate column
+// clim(0..nclim), both used as given (the caller sorts them or not, cpf.py:140-143).  The state of the reference's scan
+// is three scalars per point: the value so far (float32, cpf.py:22), `done` (its `mask`) and `primed` (its `prim`).
+// Climate row icl has level icl / (nclim-1), member iq level (iq+1) / (nens+1), both Python floats (float64) in the
+// reference.  Two quotients of whole numbers below 2^32 that differ as fractions differ by far more than an ulp and
+// equal fractions round alike, so "member level < row level" is decided exactly by cross-multiplying whole numbers; the
+// first member at or above a row's level (`cross`) never moves down from one row to the next, so it is a cursor.
+//  * members iq0 .. cross-1 prime the point where member >= row and nothing is written yet (cpf.py:41-43);
+//  * member `cross` does the three writes in the reference's order (cpf.py:45-81), then the row is finished (cpf.py:84):
+//    the lower-tail interpolation (only iq < 2; does not test `done`, sets it), the plain crossing (writes the member
+//    level, sets `done`), the upper-tail interpolation against the top row (only the last member; does not set `done`,
+//    so a later row may overwrite it).
+// The interpolation runs in T: with f32 fields the Python-float levels act as f32 scalars (NumPy 2), with f64 fields
+// everything is f64 and the store rounds to float32.  Once `done` is set and cross >= 2 no later row can change
+// anything (priming, the plain crossing and the upper tail all need !done), so the scan stops there.
+template <class T>
+EKM_HD T cpf_intersection(T tau_c, T tau_c2, T qc, T qc2, T qf) {
+  return en_add(en_mul(tau_c, en_sub(qc2, qf)), en_mul(tau_c2, en_sub(qf, qc))) / en_sub(qc2, qc);
+}
+
+template <class T, class Clim, class Ens>
+EKM_HD float cpf_point(unsigned nclim, unsigned nens, bool from_zero, Clim clim, Ens ens) {
+  float value = 0.0f;
+  bool done = false, primed = false;
+  if (nclim < 3 || nens < 1) return value;
+  const unsigned iq0 = from_zero ? 0u : nens / 2;
+  const unsigned long long dc = nclim - 1, df = (unsigned long long)nens + 1;
+  const T top = clim(nclim - 1);
+  unsigned cross = iq0;
+  for (unsigned icl = 1; icl + 1 < nclim; ++icl) {
+    while (cross < nens && (cross + 1ull) * dc < icl * df) ++cross;
+    if (done && cross >= 2) break;
+    const T qc = clim(icl);
+    for (unsigned iq = iq0; iq < cross; ++iq)
+      if (ens(iq) >= qc && !done) primed = true;
+    if (cross >= nens) continue;  // no member reaches this row's level
+    const T qf = ens(cross);
+    if (cross < 2) {  // cpf.py:47-62
+      const T qc2 = clim(icl - 1);
+      if (qf < qc && qc2 < qc && primed) {
+        const T tau_c = T((double)icl / ((double)nclim - 1.0)), tau_c2 = T((double)(icl - 1) / (double)(nclim - 1));
+        // numpy.maximum(x, 0) as recorded: the 0 comes back unless x is above it (so -0.0 gives +0.0), a NaN stays
+        const double x = (double)cpf_intersection<T>(tau_c, tau_c2, qc, qc2, qf);
+        value = (float)((x > 0.0 || x != x) ? x : 0.0);
+        done = true;
+      }
+    }
+    if (qf < qc && !done && primed) {  // cpf.py:65-67
+      value = (float)(((double)cross + 1.0) / ((double)nens + 1.0));
+      done = true;
+    }
+    if (cross == nens - 1 && qf > qc && top > qc && !done && primed) {  // cpf.py:70-81
+      const T tau_c = T((double)icl / ((double)nclim - 1.0));
+      value = (float)en_min((double)cpf_intersection<T>(tau_c, T(1), qc, top, qf), 1.0);
+    }
+  }
+  return value;
+}
+
+// cpf.py:145-155 and 86-89: `epsilon` zeroes the points whose last member is below it, compared in T, and is ignored
+// when `symmetric`; `symmetric` replaces a direct value below 0.5 by 1 - (the value of the negated, row-reversed
+// columns), formed in float32.  The reversed run does not depend on the direct one, so it runs only where it is read.
+template <class T, class Clim, class Ens>
+EKM_HD float cpf_value(unsigned nclim, unsigned nens, bool from_zero, bool symmetric, bool use_epsilon, T epsilon,
+                       Clim clim, Ens ens) {
+  float value = cpf_point<T>(nclim, nens, from_zero, clim, ens);
+  if (symmetric) {
+    if (value < 0.5f)
+      value = en_sub(1.0f, cpf_point<T>(
+                               nclim, nens, from_zero, [&](unsigned i) -> T { return -clim(nclim - 1 - i); },
+                               [&](unsigned j) -> T { return -ens(nens - 1 - j); }));
+  } else if (use_epsilon && ens(nens - 1) < epsilon) {
+    value = 0.0f;
+  }
+  return value;
 }
 
 // quantiles.py:60-84: one quantile level of one point.  The position record (lo, hi, w) of the level is computed by the

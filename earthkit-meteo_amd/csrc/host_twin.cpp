@@ -205,6 +205,43 @@ EKM_HOST_ENSEMBLE(f32, float)
 EKM_HOST_ENSEMBLE(f64, double)
 #undef EKM_HOST_ENSEMBLE
 
+// ---- cpf: cpf_value of ensemble_point.hpp on the CPU, same arguments as ekm_cpf_* without dev / stream ----
+template <class T>
+static void host_stage_column(const T* field, unsigned rows, size_t npts, size_t p, std::vector<T>& col, bool sort) {
+  for (unsigned m = 0; m < rows; ++m) {
+    const T x = field[(size_t)m * npts + p];
+    if (sort)
+      ekm::ens_insert_nan_last<T>(m, x, [&](unsigned j) { return col[j]; }, [&](unsigned j, T v) { col[j] = v; });
+    else
+      col[m] = x;
+  }
+}
+
+template <class T>
+static int host_cpf(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts, int sort_clim, int sort_ens,
+                    int from_zero, int symmetric, int use_epsilon, double epsilon, float* out) {
+  if (nclim < 1 || nens < 1) return -2;
+  std::vector<T> ccol(nclim), ecol(nens);
+  for (size_t p = 0; p < npts; ++p) {
+    host_stage_column<T>(clim, nclim, npts, p, ccol, sort_clim != 0);
+    host_stage_column<T>(ens, nens, npts, p, ecol, sort_ens != 0);
+    out[p] = ekm::cpf_value<T>(
+        nclim, nens, from_zero != 0, symmetric != 0, use_epsilon != 0, T(epsilon), [&](unsigned i) { return ccol[i]; },
+        [&](unsigned j) { return ecol[j]; });
+  }
+  return 0;
+}
+#define EKM_HOST_CPF(tag, T)                                                                                         \
+  extern "C" int ekm_host_cpf_##tag(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts,         \
+                                    int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,      \
+                                    double epsilon, float* out) {                                                    \
+    return host_cpf<T>(clim, ens, nclim, nens, npts, sort_clim, sort_ens, from_zero, symmetric, use_epsilon, epsilon, \
+                       out);                                                                                         \
+  }
+EKM_HOST_CPF(f32, float)
+EKM_HOST_CPF(f64, double)
+#undef EKM_HOST_CPF
+
 // ---- quantiles: quantile_point of ensemble_point.hpp on the CPU, same arguments as ekm_quantiles_* without dev / stream ----
 template <class T, class Out>
 static int host_quantiles(const T* arr, size_t outer, unsigned m, size_t inner, const double* lo, const double* hi,

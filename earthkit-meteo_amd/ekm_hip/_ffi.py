@@ -91,6 +91,7 @@ def _signatures():
         sig[f"ekm_efi_{tag}"] = ([i, vp, vp, vp, u32, u32, sz, dbl, vp, vp, vp, vp], i)
         sig[f"ekm_sot_{tag}"] = ([i, vp, vp, vp, vp, u32, sz, i, dbl, vp], i)
         sig[f"ekm_sot_func_{tag}"] = ([i, vp, vp, vp, vp, sz, dbl, dbl, dbl, vp], i)
+        sig[f"ekm_cpf_{tag}"] = ([i, vp, vp, vp, u32, u32, sz, i, i, i, i, i, dbl, vp], i)
         sig[f"ekm_crps_from_ensemble_{tag}"] = ([i, vp, vp, vp, u32, sz, vp, vp, vp, vp], i)
     for tag in ("f32", "f64", "f32_f64"):
         sig[f"ekm_quantiles_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp, vp, u32, i, vp], i)

@@ -1,18 +1,29 @@
-"""`earthkit.meteo.extreme` on MI355X: Extreme Forecast Index and Shift of Tails of an ensemble against a model
-climate (reference extreme/array/efi.py, extreme/array/sot.py; kernels csrc/ensemble.hip).
+"""`earthkit.meteo.extreme` on MI355X: Extreme Forecast Index, Shift of Tails and Crossing Point Forecast of an
+ensemble against a model climate (reference extreme/array/efi.py, extreme/array/sot.py, extreme/array/cpf.py; kernels
+csrc/ensemble.hip).
 
 Same names, argument order, defaults and error conventions as the reference.  NumPy in -> NumPy out; `DeviceArray` in
 -> `DeviceArray` out; device tensors of another ROCm library are taken over through DLPack and handed back in that
 library's type.  Fields are member-major: `clim` [nclim, npoints], `ens` [nens, npoints]; at most 256 members in f32 and
-128 in f64 (more raises `EkmError`).
+128 in f64 (more raises `EkmError`).  `cpf` has its own limit: the members, plus the climate rows when `sort_clim`, may
+number 640 in f32 and 320 in f64.
 
 The arithmetic runs in f32 when every array argument is f32 and in f64 otherwise (f64, mixed, integer).  In f32 and in
 f64 the results equal the reference's bit for bit.  Deviation: with mixed dtypes the reference's `efi` forms `frac` in
 `clim`'s dtype (so in f32 when only `clim` is f32) while this computes in f64; the two differ by the rounding of `frac`
 and `dFdp` to f32 (about 1e-8 absolute on the index, see tests/_ensemble_numpy.py::mixed_efi_bound).
 
-`cpf` (marked experimental in the reference, a stateful scan) and `sot_unsorted` (raises on every call in the
-reference) are not provided.
+`cpf` (marked experimental in the reference) returns float32 for every input dtype, as the reference does, and keeps
+the reference's oddities: a column with a NaN does not give NaN (numpy.sort puts the NaN last and the scan compares as
+usual), the lower-tail interpolation overwrites a crossing that is already written, the upper-tail one may be
+overwritten by a later row.  Deviation: with mixed dtypes `cpf` computes in f64 on the upcast columns, while the
+reference lets NumPy promote operation by operation, so with `clim` f32 and `ens` f64 it forms the differences of two
+climate rows in f32 (the denominator of both interpolations).  Only interpolated values can differ, by at most
+3 * 2^-24 relative (derived in tests/_cpf_numpy.py::mixed_cpf_bound; on the recorded mixed cases no point differs);
+levels written by a plain crossing are equal.  With `clim` f64 and `ens` f32 the reference's arithmetic is f64 as here,
+except that it compares `epsilon` rounded to f32.
+
+`sot_unsorted` (raises on every call in the reference) is not provided.
 """
 import numpy as np
 
@@ -55,6 +66,34 @@ def efi(clim, ens, eps=-0.1):
     _e._ffi.check(getattr(_e.lib(), f"ekm_efi_{_e.tag_of(dtype)}")(
         device, stream, d_clim.ptr, d_ens.ptr, nclim, nens, npts, eps, tabs[0].on(stream), tabs[1].on(stream),
         tabs[2].on(stream), out.on(stream)))
+    return _e.finish(out, _e.on_device(clim, ens))
+
+
+@_foreign_aware("clim", "ens")
+def cpf(clim, ens, sort_clim=True, sort_ens=True, epsilon=None, symmetric=False, from_zero=False):
+    """Crossing Point Forecast (cpf.py:94-155).  clim: (nclim, npoints) per-point climatology; ens: (nens, npoints).
+    sort_clim / sort_ens: sort the columns first (a NaN goes last, as numpy.sort puts it), else they are used as given.
+    epsilon: points whose last member is below it give 0; ignored when `symmetric`.  symmetric: values below 0.5 become
+    1 - (the CPF of the negated fields).  from_zero: look for the crossing from the lowest member, not from the median.
+    Returns float32 (npoints); one kernel launch per call.  The inputs are never written."""
+    clim, ens = _e.as_input(clim), _e.as_input(ens)
+    if len(clim.shape) != 2 or len(ens.shape) != 2:
+        raise ValueError(f"cpf: clim and ens must be 2-D (nclim, npoints) and (nens, npoints), got {tuple(clim.shape)} and {tuple(ens.shape)}")
+    nclim, npts = (int(v) for v in clim.shape)
+    nens, npts_ens = (int(v) for v in ens.shape)
+    assert npts == npts_ens  # cpf.py:138
+    if nens < 1 or nclim < 1:
+        raise ValueError("cpf: clim and ens need at least one row each")
+    use_epsilon = epsilon is not None and not symmetric  # cpf.py:145-146
+    dtype = _e.arith_dtype(clim, ens)
+    device, stream, keep = _e.device_of(clim, ens), current_stream(), []
+    d_clim = _e.upload(clim, dtype, device, stream, keep)
+    d_ens = _e.upload(ens, dtype, device, stream, keep)
+    out = DeviceArray.empty((npts,), _F32, device)
+    _e._ffi.check(getattr(_e.lib(), f"ekm_cpf_{_e.tag_of(dtype)}")(
+        device, stream, d_clim.ptr, d_ens.ptr, nclim, nens, npts, int(bool(sort_clim)), int(bool(sort_ens)),
+        int(bool(from_zero)), int(bool(symmetric)), int(use_epsilon), float(epsilon) if use_epsilon else 0.0,
+        out.on(stream)))
     return _e.finish(out, _e.on_device(clim, ens))
 
 

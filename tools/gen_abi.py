@@ -173,7 +173,8 @@ typedef struct ekm_operand {
  *      ekm_host_register, ekm_host_unregister removed; "table_tiles" default 8 -> 0 (= by op); field pointers must be
  *      aligned to their element size; at most 32 KiB (was 64) of staged level vectors per launch.
  *      Added since, without a bump (an addition breaks no client): the vertical interpolation entry points; the ensemble
- *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*; the per-point quantiles ekm_quantiles_*. */
+ *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*; the per-point quantiles ekm_quantiles_*; the
+ *      Crossing Point Forecast ekm_cpf_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -364,9 +365,9 @@ EKM_API int ekm_interpolate_hybrid_to_pressure_f64(int dev, void* stream, const 
                                                    const double* aux_min_coord, const double* aux_max_data,
                                                    const double* aux_max_coord, uint32_t aux_field_mask, double* out);
 
-/* ---- ensemble reductions: Extreme Forecast Index, Shift of Tails, CRPS ----
+/* ---- ensemble reductions: Extreme Forecast Index, Shift of Tails, Crossing Point Forecast, CRPS ----
  * One lane per grid point; fields are member-major: clim [nclim, npts], ens / x [nens, npts] (quantiles: any axis).  The point's ensemble is
- * sorted in LDS: nens <= 256 (_f32) / 128 (_f64), more members return EKM_ERR_ARG.  Every operation is rounded once in
+ * sorted in LDS: nens <= 256 (_f32) / 128 (_f64), more members return EKM_ERR_ARG (cpf: its own limit, below).  Every operation is rounded once in
  * the reference's order and the f64 sums run in its loop order: the results equal the reference's (NumPy) bit for bit.
  * Like every compute entry point these only enqueue a kernel: nothing allocates, copies or waits on the host.
  *
@@ -395,6 +396,22 @@ EKM_API int ekm_sot_func_f32(int dev, void* stream, const float* qc_tail, const 
                              double eps, double lower_bound, double upper_bound, float* out);
 EKM_API int ekm_sot_func_f64(int dev, void* stream, const double* qc_tail, const double* qc, const double* qf, size_t n,
                              double eps, double lower_bound, double upper_bound, double* out);
+/* cpf: reference extreme/array/cpf.py:13-155, the Crossing Point Forecast, one launch per call (`symmetric` included).
+ * The flags are 0 / non-zero.  sort_clim, sort_ens (cpf.py:140-143): the column is sorted as numpy.sort does, a NaN above
+ * every number, else used as given; the inputs are never written.  from_zero (cpf.py:27): the scan starts at member 0,
+ * else at nens / 2.  symmetric (cpf.py:145-153): a direct value below 0.5 becomes 1 - (the value of the negated,
+ * row-reversed columns); epsilon is then ignored.  use_epsilon, epsilon (cpf.py:86-89): points whose last member is below
+ * epsilon (compared in the input dtype) give 0.
+ * The ensemble column, and the climate column when sort_clim, are held in LDS:
+ * (nens + (sort_clim ? nclim : 0)) * 64 * sizeof(element) <= 160 KiB, i.e. 640 rows (_f32) / 320 rows (_f64); more
+ * returns EKM_ERR_ARG and writes nothing.  nclim < 3 gives 0 everywhere.
+ * out: float [npts] for both input dtypes (cpf.py:22); _f32 interpolates in float, _f64 in double, rounded on the store. */
+EKM_API int ekm_cpf_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens,
+                        size_t npts, int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,
+                        double epsilon, float* out);
+EKM_API int ekm_cpf_f64(int dev, void* stream, const double* clim, const double* ens, uint32_t nclim, uint32_t nens,
+                        size_t npts, int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,
+                        double epsilon, float* out);
 /* crps_from_ensemble: reference score/array/ensemble.py:34-82.  x: [nens, npts], y: [npts]; p2[i] = (i/nens)^2 and
  * q2[i] = (1 - i/nens)^2, i = 0..nens, float64 on the device (computed by the caller as the reference computes them).
  * out: float64 [npts], NaN where x or y holds a NaN; missing (may be NULL): one byte per point, 1 exactly there -- the
