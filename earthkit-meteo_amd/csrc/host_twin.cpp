@@ -12,6 +12,7 @@
 #include "ensemble_point.hpp"
 #include "interp_point.hpp"
 #include "ops.hpp"
+#include "solar_point.hpp"
 
 // Ops that keep a per-workgroup LDS table on the device (ops.hpp::OpTable, the bisection lattice) take the SAME path
 // here -- table filled once, OpTable<Op>::apply per point -- so the table arithmetic the kernels run is what the golden
@@ -241,6 +242,33 @@ static int host_cpf(const T* clim, const T* ens, unsigned nclim, unsigned nens, 
 EKM_HOST_CPF(f32, float)
 EKM_HOST_CPF(f64, double)
 #undef EKM_HOST_CPF
+
+// ---- solar: solar_point of solar_point.hpp on the CPU, the operands described as for ekm_solar_* (mode, len, inner) ----
+template <class T, class Out>
+static int host_solar(const T* lat, int lat_mode, unsigned long long lat_len, unsigned long long lat_inner, const T* lon,
+                      int lon_mode, unsigned long long lon_len, unsigned long long lon_inner, const double* nodes,
+                      unsigned nnodes, Out* out, size_t n) {
+  const ekm::SolarOperand<T> la{lat, lat_mode, lat_len ? lat_len : 1, lat_inner ? lat_inner : 1};
+  const ekm::SolarOperand<T> lo{lon, lon_mode, lon_len ? lon_len : 1, lon_inner ? lon_inner : 1};
+  for (size_t p = 0; p < n; ++p)
+    out[p] = ekm::solar_point<Out>(ekm::solar_fetch<T>(la, p, false), ekm::solar_fetch<T>(lo, p, false), nnodes,
+                                   [&](unsigned k, int j) { return nodes[(size_t)k * ekm::kSolarRecord + j]; });
+  return 0;
+}
+#define EKM_HOST_SOLAR(tag, T, Out)                                                                                      \
+  extern "C" int ekm_host_solar_##tag(const T* lat, int lat_mode, unsigned long long lat_len, unsigned long long lat_inner, \
+                                      const T* lon, int lon_mode, unsigned long long lon_len, unsigned long long lon_inner, \
+                                      const double* nodes, unsigned nnodes, Out* out, size_t n) {                        \
+    return host_solar<T, Out>(lat, lat_mode, lat_len, lat_inner, lon, lon_mode, lon_len, lon_inner, nodes, nnodes, out, n); \
+  }
+EKM_HOST_SOLAR(f32, float, float)
+EKM_HOST_SOLAR(f64, double, double)
+EKM_HOST_SOLAR(f32_f64, float, double)
+#undef EKM_HOST_SOLAR
+// (for the tests of the sine / cosine themselves)
+extern "C" void ekm_host_sincos_deg(const double* x, double* s, double* c, size_t n) {
+  for (size_t i = 0; i < n; ++i) ekm::sol_sincos_deg(x[i], s[i], c[i]);
+}
 
 // ---- quantiles: quantile_point of ensemble_point.hpp on the CPU, same arguments as ekm_quantiles_* without dev / stream ----
 template <class T, class Out>

@@ -174,7 +174,7 @@ typedef struct ekm_operand {
  *      aligned to their element size; at most 32 KiB (was 64) of staged level vectors per launch.
  *      Added since, without a bump (an addition breaks no client): the vertical interpolation entry points; the ensemble
  *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*; the per-point quantiles ekm_quantiles_*; the
- *      Crossing Point Forecast ekm_cpf_*. */
+ *      Crossing Point Forecast ekm_cpf_*; the solar geometry ekm_solar_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -440,6 +440,23 @@ EKM_API int ekm_quantiles_f64(int dev, void* stream, const double* arr, size_t o
                               const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
 EKM_API int ekm_quantiles_f32_f64(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
                                   const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
+
+/* ---- solar geometry: cosine of the solar zenith angle, its time average, top-of-atmosphere incident radiation ----
+ * Reference solar/array/solar.py:51-96 (cos_solar_zenith_angle), :99-179 (_integrate), :182-254.  One launch, one lane per
+ * point: out[i] = sum over the nnodes time nodes of w * (isr * max0(p * sin(lat) + q * cos(lat) cos(lon) + r * cos(lat) sin(lon))),
+ * max0(z) = z < 0 ? 0 : z (a NaN stays).  lat, lon: degrees, each an ekm_operand in mode EKM_FIELD, EKM_SCALAR,
+ * EKM_LEVEL_MAJOR or EKM_LEVEL_MINOR (any len >= 1, inner >= 1; len * inner must cover n).  nodes: nnodes records of five
+ * float64 on the device, (p, q, r, w, isr) with p = sin(dec), q = cos(dec) cos(a), r = -cos(dec) sin(a), a the node's hour
+ * angle plus time correction: the caller computes them as the reference computes its dates, weights, declinations and
+ * time corrections (solar.py:27-48, :150-177, :225-229); the instantaneous function is one node with w = isr = 1.
+ * All arithmetic is double on the upcast inputs, the result is rounded once: _f32 float in, float out; _f64 double in,
+ * double out; _f32_f64 float in, double out.  Only enqueues a kernel: nothing allocates, copies or waits on the host. */
+EKM_API int ekm_solar_f32(int dev, void* stream, const ekm_operand* lat, const ekm_operand* lon, const double* nodes,
+                          uint32_t nnodes, float* out, size_t n);
+EKM_API int ekm_solar_f64(int dev, void* stream, const ekm_operand* lat, const ekm_operand* lon, const double* nodes,
+                          uint32_t nnodes, double* out, size_t n);
+EKM_API int ekm_solar_f32_f64(int dev, void* stream, const ekm_operand* lat, const ekm_operand* lon, const double* nodes,
+                              uint32_t nnodes, double* out, size_t n);
 
 /* ---- thermo entry points ----
  * Argument order: dev, stream, inputs..., enum parameters..., [eps], outputs..., n. */
