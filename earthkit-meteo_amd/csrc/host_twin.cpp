@@ -13,6 +13,7 @@
 #include "interp_point.hpp"
 #include "ops.hpp"
 #include "solar_point.hpp"
+#include "wind_point.hpp"
 
 // Ops that keep a per-workgroup LDS table on the device (ops.hpp::OpTable, the bisection lattice) take the SAME path
 // here -- table filled once, OpTable<Op>::apply per point -- so the table arithmetic the kernels run is what the golden
@@ -297,3 +298,82 @@ EKM_HOST_QUANTILES(f32, float, float)
 EKM_HOST_QUANTILES(f64, double, double)
 EKM_HOST_QUANTILES(f32_f64, float, double)
 #undef EKM_HOST_QUANTILES
+
+// ---- wind: wind_point of wind_point.hpp on the CPU, the operands described as for ekm_wind_* (mode, len, inner); a null
+// output is not written ----
+template <class T, int KIND, int MODE, int WHICH>
+static void host_wind_as(const ekm::SolarOperand<T>& a, const ekm::SolarOperand<T>& b, T* out0, T* out1, size_t n) {
+  for (size_t p = 0; p < n; ++p) {
+    T o0, o1;
+    ekm::wind_point<T, KIND, MODE, WHICH>((T)ekm::solar_fetch<T>(a, p, false),
+                                          KIND == ekm::WIND_KIND_CORIOLIS ? T(0) : (T)ekm::solar_fetch<T>(b, p, false), o0, o1);
+    if (out0) out0[p] = (T)o0;
+    if (out1) out1[p] = (T)o1;
+  }
+}
+template <class T>
+static int host_wind(int kind, const T* a, int a_mode, unsigned long long a_len, unsigned long long a_inner, const T* b, int b_mode,
+                     unsigned long long b_len, unsigned long long b_inner, int mode, T* out0, T* out1, size_t n) {
+  const ekm::SolarOperand<T> oa{a, a_mode, a_len ? a_len : 1, a_inner ? a_inner : 1};
+  const ekm::SolarOperand<T> ob{b ? b : a, b ? b_mode : a_mode, b_len ? b_len : 1, b_inner ? b_inner : 1};
+  using namespace ekm;
+  if (kind == WIND_KIND_POLAR && mode == WIND_METEO) host_wind_as<T, WIND_KIND_POLAR, WIND_METEO, 3>(oa, ob, out0, out1, n);
+  else if (kind == WIND_KIND_POLAR && mode == WIND_POLAR_POSITIVE) host_wind_as<T, WIND_KIND_POLAR, WIND_POLAR_POSITIVE, 3>(oa, ob, out0, out1, n);
+  else if (kind == WIND_KIND_POLAR && mode == WIND_POLAR_SIGNED) host_wind_as<T, WIND_KIND_POLAR, WIND_POLAR_SIGNED, 3>(oa, ob, out0, out1, n);
+  else if (kind == WIND_KIND_XY && mode == WIND_METEO) host_wind_as<T, WIND_KIND_XY, WIND_METEO, 3>(oa, ob, out0, out1, n);
+  else if (kind == WIND_KIND_XY && mode == WIND_POLAR_POSITIVE) host_wind_as<T, WIND_KIND_XY, WIND_POLAR_POSITIVE, 3>(oa, ob, out0, out1, n);
+  else if (kind == WIND_KIND_CORIOLIS) host_wind_as<T, WIND_KIND_CORIOLIS, WIND_METEO, 1>(oa, ob, out0, out1, n);
+  else return -1;
+  return 0;
+}
+// the wind rose: the count and the finish of wind.hip, one sample after the other
+template <class T>
+static int host_windrose(const T* speed, const T* dir, size_t n, const double* edges, unsigned ns, unsigned nd, double inv_step,
+                         int percent, double* out) {
+  if (ns < 2 || nd < 3) return -1;
+  const unsigned rows = ns - 1, cols = nd - 1;
+  std::vector<unsigned long long> table((size_t)rows * cols, 0ull);
+  const double* se = edges;
+  const double* de = edges + ns;
+  unsigned long long total = 0;
+  for (size_t p = 0; p < n; ++p) {
+    const int cell = ekm::wind_cell((double)speed[p], (double)dir[p], [&](unsigned k) { return se[k]; }, ns,
+                                    [&](unsigned k) { return de[k]; }, nd, inv_step);
+    if (cell >= 0) {
+      table[(size_t)cell] += 1;
+      total += 1;
+    }
+  }
+  for (unsigned r = 0; r < rows; ++r)
+    for (unsigned c = 0; c + 1 < cols; ++c)
+      out[(size_t)r * (cols - 1) + c] =
+          ekm::wind_rose_value(table[(size_t)r * cols + c] + (c == 0 ? table[(size_t)r * cols + cols - 1] : 0ull), total, percent);
+  return 0;
+}
+#define EKM_HOST_WIND(tag, T)                                                                                                      \
+  extern "C" int ekm_host_wind_##tag(int kind, const T* a, int a_mode, unsigned long long a_len, unsigned long long a_inner,       \
+                                     const T* b, int b_mode, unsigned long long b_len, unsigned long long b_inner, int mode,       \
+                                     T* out0, T* out1, size_t n) {                                                                 \
+    return host_wind<T>(kind, a, a_mode, a_len, a_inner, b, b_mode, b_len, b_inner, mode, out0, out1, n);                          \
+  }                                                                                                                                \
+  extern "C" int ekm_host_windrose_##tag(const T* speed, const T* dir, size_t n, const double* edges, unsigned ns, unsigned nd,    \
+                                         double inv_step, int percent, double* out) {                                              \
+    return host_windrose<T>(speed, dir, n, edges, ns, nd, inv_step, percent, out);                                                 \
+  }
+EKM_HOST_WIND(f32, float)
+EKM_HOST_WIND(f64, double)
+#undef EKM_HOST_WIND
+// (for the tests of the primitives themselves)
+extern "C" void ekm_host_wind_primitives_f32(const float* y, const float* x, float* at, float* hy, float* sn, float* cs, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    at[i] = ekm::wind_atan2(y[i], x[i]);
+    hy[i] = ekm::wind_hypot(x[i], y[i]);
+    ekm::wind_sincos_deg(x[i], sn[i], cs[i]);
+  }
+}
+extern "C" void ekm_host_atan2_hypot(const double* y, const double* x, double* at, double* hy, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    at[i] = ekm::wind_atan2(y[i], x[i]);
+    hy[i] = ekm::wind_hypot(x[i], y[i]);
+  }
+}

@@ -93,6 +93,11 @@ def _signatures():
         sig[f"ekm_sot_func_{tag}"] = ([i, vp, vp, vp, vp, sz, dbl, dbl, dbl, vp], i)
         sig[f"ekm_cpf_{tag}"] = ([i, vp, vp, vp, u32, u32, sz, i, i, i, i, i, dbl, vp], i)
         sig[f"ekm_crps_from_ensemble_{tag}"] = ([i, vp, vp, vp, u32, sz, vp, vp, vp, vp], i)
+        op = C.POINTER(Operand)
+        sig[f"ekm_wind_polar_{tag}"] = ([i, vp, op, op, i, vp, vp, sz], i)
+        sig[f"ekm_wind_xy_{tag}"] = ([i, vp, op, op, i, vp, vp, sz], i)
+        sig[f"ekm_wind_coriolis_{tag}"] = ([i, vp, op, vp, sz], i)
+        sig[f"ekm_windrose_{tag}"] = ([i, vp, vp, vp, sz, vp, u32, u32, dbl, i, vp, vp], i)
     for tag in ("f32", "f64", "f32_f64"):
         sig[f"ekm_quantiles_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp, vp, u32, i, vp], i)
         sig[f"ekm_solar_{tag}"] = ([i, vp, C.POINTER(Operand), C.POINTER(Operand), vp, u32, vp, sz], i)

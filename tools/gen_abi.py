@@ -174,7 +174,8 @@ typedef struct ekm_operand {
  *      aligned to their element size; at most 32 KiB (was 64) of staged level vectors per launch.
  *      Added since, without a bump (an addition breaks no client): the vertical interpolation entry points; the ensemble
  *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*; the per-point quantiles ekm_quantiles_*; the
- *      Crossing Point Forecast ekm_cpf_*; the solar geometry ekm_solar_*. */
+ *      Crossing Point Forecast ekm_cpf_*; the solar geometry ekm_solar_*; the wind functions
+ *      ekm_wind_polar_*, ekm_wind_xy_*, ekm_wind_coriolis_*, ekm_windrose_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -457,6 +458,41 @@ EKM_API int ekm_solar_f64(int dev, void* stream, const ekm_operand* lat, const e
                           uint32_t nnodes, double* out, size_t n);
 EKM_API int ekm_solar_f32_f64(int dev, void* stream, const ekm_operand* lat, const ekm_operand* lon, const double* nodes,
                               uint32_t nnodes, double* out, size_t n);
+
+/* ---- wind: speed and direction, polar <-> xy, the Coriolis parameter, the wind rose ----
+ * Reference wind/array/wind.py:15-189, :225-328.  The three elementwise entry points take ekm_operands in mode EKM_FIELD,
+ * EKM_SCALAR, EKM_LEVEL_MAJOR or EKM_LEVEL_MINOR (as ekm_solar_*), read every operand once and write every output once;
+ * the arithmetic is float in the _f32 entry points and double in the _f64 ones.
+ *  ekm_wind_polar_*: speed = hypot(u, v) and direction [degrees] from d = atan2(v, u); either output may be NULL and is
+ *    then neither computed nor written.  mode 0 (meteo): d <= -pi/2 ? (-pi/2 - d) deg : (1.5 pi - d) deg, deg = 180/pi;
+ *    mode 1 (polar, to_positive): d deg, plus 360 where that is negative; mode 2 (polar, signed): d deg.
+ *  ekm_wind_xy_*: x = m cos(a), y = m sin(a) with a = 270 - direction degrees (mode 0, meteo) or a = direction (mode 1);
+ *    the angle is reduced exactly in degrees.
+ *  ekm_wind_coriolis_*: 2 Omega sin(lat degrees), Omega = 7.292115083046062e-05 1/s.
+ *  ekm_windrose_*: the two-dimensional histogram np.histogram2d(speed, direction, [speed edges, direction edges]) of n
+ *    samples with the last direction column added to the first and dropped.  edges: ns speed edges followed by nd
+ *    direction edges, float64 on the device, each non-decreasing (ns >= 2, nd >= 3, ns + nd <= 2048); bin k holds
+ *    e[k] <= x < e[k+1], the last bin also x == e[last]; a NaN or a value outside either axis drops the sample.
+ *    inv_step: (nd - 1) / (last - first direction edge), a first guess only (any finite value gives the same counts).
+ *    table: (ns-1)*(nd-1) 64-bit counters of scratch on the device, zeroed by the call; out: [ns-1][nd-2] float64, the
+ *    counts, or with percent != 0 count * 100 / (number of counted samples) (NaN when none).  Enqueues a memset and two kernels.
+ * Nothing here allocates, copies or waits on the host. */
+EKM_API int ekm_wind_polar_f32(int dev, void* stream, const ekm_operand* u, const ekm_operand* v, int mode, float* speed,
+                               float* direction, size_t n);
+EKM_API int ekm_wind_xy_f32(int dev, void* stream, const ekm_operand* magnitude, const ekm_operand* direction, int mode,
+                            float* x, float* y, size_t n);
+EKM_API int ekm_wind_coriolis_f32(int dev, void* stream, const ekm_operand* lat, float* out, size_t n);
+EKM_API int ekm_windrose_f32(int dev, void* stream, const float* speed, const float* direction, size_t n, const double* edges,
+                             uint32_t ns, uint32_t nd, double inv_step, int percent, unsigned long long* table,
+                             double* out);
+EKM_API int ekm_wind_polar_f64(int dev, void* stream, const ekm_operand* u, const ekm_operand* v, int mode, double* speed,
+                               double* direction, size_t n);
+EKM_API int ekm_wind_xy_f64(int dev, void* stream, const ekm_operand* magnitude, const ekm_operand* direction, int mode,
+                            double* x, double* y, size_t n);
+EKM_API int ekm_wind_coriolis_f64(int dev, void* stream, const ekm_operand* lat, double* out, size_t n);
+EKM_API int ekm_windrose_f64(int dev, void* stream, const double* speed, const double* direction, size_t n, const double* edges,
+                             uint32_t ns, uint32_t nd, double inv_step, int percent, unsigned long long* table,
+                             double* out);
 
 /* ---- thermo entry points ----
  * Argument order: dev, stream, inputs..., enum parameters..., [eps], outputs..., n. */
