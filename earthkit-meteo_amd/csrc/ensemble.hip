@@ -1,7 +1,7 @@
-// Ensemble reductions on gfx950: Extreme Forecast Index, Shift of Tails, Crossing Point Forecast, CRPS and per-point
-// quantiles.
+// Ensemble reductions on gfx950: Extreme Forecast Index, Shift of Tails, Crossing Point Forecast, CRPS, per-point
+// quantiles and the Gumbel extreme-value fit with its cdf and ppf.
 // Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, extreme/array/cpf.py:13-155,
-// score/array/ensemble.py:34-82, stats/array/quantiles.py:18-84.
+// score/array/ensemble.py:34-82, stats/array/quantiles.py:18-84, stats/array/extreme_values.py:24-155.
 //
 // One kernel family: one lane per grid point, one wave (64 lanes) per workgroup.  The fields are member-major,
 // ens [nens, npts] and clim [nclim, npts], so a wave reads a member row as one coalesced run.  The lane's ensemble is
@@ -17,6 +17,10 @@
 //          [outer, m, inner] and point p = o * inner + i reads sample j at (o * m + j) * inner + i.  With the sample axis
 //          last (inner == 1) every lane reads its own contiguous column; staging the wave's run through LDS first was
 //          measured slower and is not kept (profiles/HISTORY.md).
+//  * gumbel_fit: the first two L-moments of the sorted column, summed in float64 in the reference polyfill's order, then
+//          mu and sigma (extreme_values.py:44-64); [outer, m, inner] addressing as for quantiles.  Traffic: m elements
+//          read, 16 B written per point.  gumbel_cdf / gumbel_ppf are plain outer products of nx levels and npts points
+//          (256 lanes per workgroup, no LDS): 16 B read and 8 nx B written per point.
 //  * cpf:  the crossing-point scan of the sorted ensemble against the interior climate rows, `symmetric` included, in one
 //          launch.  The ensemble column always goes to LDS (sorted NaN-last, or copied as given): the scan re-reads
 //          members for every row.  The climate goes to LDS only when it has to be sorted; as given it streams from
@@ -124,6 +128,49 @@ __global__ __launch_bounds__(kEnsLanes) void quantile_points(const T* __restrict
   auto s = [&](unsigned k) -> T { return col[k * kEnsLanes]; };
   for (unsigned k = 0; k < nq; ++k)
     out[(unsigned long long)k * npts + p] = quantile_point<T, Out>(has_nan, s, (unsigned)lo[k], (unsigned)hi[k], w[k], mode);
+}
+
+// extreme_values.py:44-64.  sample: [outer, m, inner] as for quantile_points; mu, sigma: float64 [npts].
+static_assert(kGumbelCdf == EKM_GUMBEL_CDF && kGumbelReturnPeriod == EKM_GUMBEL_RETURN_PERIOD, "ensemble_point.hpp and the header disagree");
+
+template <class T>
+__global__ __launch_bounds__(kEnsLanes) void gumbel_fit_points(const T* __restrict__ sample, unsigned m,
+                                                               unsigned long long inner, unsigned long long npts,
+                                                               double* __restrict__ mu, double* __restrict__ sigma) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
+  if (p >= npts) return;
+  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
+  const unsigned long long o = p / inner, i = p - o * inner;
+  const bool has_nan = sort_members<T>(sample + o * m * inner + i, inner, m, col, false, T(0));
+  double mu_p, sigma_p;
+  gumbel_fit_point<T>(m, has_nan, [&](unsigned k) -> T { return col[k * kEnsLanes]; }, mu_p, sigma_p);
+  mu[p] = mu_p;
+  sigma[p] = sigma_p;
+}
+
+// extreme_values.py:76-110: the outer product of nx levels and npts points, out[k * npts + p].  One lane per point keeps
+// mu and sigma in registers across the levels; the level table is the same address for every lane of a wave.
+constexpr int kGumbelLanes = 256;
+
+__global__ __launch_bounds__(kGumbelLanes) void gumbel_cdf_points(const double* __restrict__ mu,
+                                                                  const double* __restrict__ sigma,
+                                                                  unsigned long long npts, const double* __restrict__ x,
+                                                                  unsigned nx, double freq, int mode,
+                                                                  double* __restrict__ out) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * kGumbelLanes + threadIdx.x;
+  if (p >= npts) return;
+  const double m = mu[p], s = sigma[p];
+  for (unsigned k = 0; k < nx; ++k) out[(unsigned long long)k * npts + p] = gumbel_cdf_point(m, s, x[k], freq, mode);
+}
+
+__global__ __launch_bounds__(kGumbelLanes) void gumbel_ppf_points(const double* __restrict__ mu,
+                                                                  const double* __restrict__ sigma,
+                                                                  unsigned long long npts, const double* __restrict__ t,
+                                                                  unsigned nt, double* __restrict__ out) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * kGumbelLanes + threadIdx.x;
+  if (p >= npts) return;
+  const double m = mu[p], s = sigma[p];
+  for (unsigned k = 0; k < nt; ++k) out[(unsigned long long)k * npts + p] = gumbel_ppf_point(m, s, t[k]);
 }
 
 // Streams the `rows` values of one point (row j at base[j * stride]) into the lane's LDS column: sorted as numpy.sort
@@ -339,9 +386,84 @@ static int launch_quantiles(int dev, void* stream, const T* arr, size_t outer, u
   return ens_launched("quantiles");
 }
 
+template <class T>
+static int launch_gumbel_fit(int dev, void* stream, const T* sample, size_t outer, uint32_t m, size_t inner, double* mu,
+                             double* sigma) {
+  if (outer == 0 || inner == 0) return EKM_OK;
+  if (m < 2) return set_error(EKM_ERR_ARG, "gumbel_fit: at least two samples are required, got %u", m);
+  if (inner > ~(size_t)0 / outer) return set_error(EKM_ERR_ARG, "gumbel_fit: too many points");
+  const size_t npts = outer * inner;
+  for (const double* ptr : {mu, sigma})
+    if (!ptr || reinterpret_cast<uintptr_t>(ptr) % sizeof(double))
+      return set_error(EKM_ERR_ARG, "gumbel_fit: mu or sigma is null or not 8-B aligned");
+  unsigned grid;
+  size_t lds;
+  int rc = ens_prepare<T>(dev, "gumbel_fit", npts, m, {sample}, &grid, &lds);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL((gumbel_fit_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), sample, m,
+                     (unsigned long long)inner, (unsigned long long)npts, mu, sigma);
+  return ens_launched("gumbel_fit");
+}
+
+// The argument checks the two outer-product entry points share; returns the grid size in *grid
+static int gumbel_prepare(int dev, const char* what, size_t npts, uint32_t nlev, std::initializer_list<const void*> ptrs,
+                          unsigned* grid) {
+  for (const void* ptr : ptrs) {
+    if (!ptr) return set_error(EKM_ERR_ARG, "%s: null pointer", what);
+    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(double))
+      return set_error(EKM_ERR_ARG, "%s: a pointer is not 8-B aligned", what);
+  }
+  if (npts > ~(size_t)0 / sizeof(double) / nlev) return set_error(EKM_ERR_ARG, "%s: too many points", what);
+  const unsigned long long g = ((unsigned long long)npts + kGumbelLanes - 1) / kGumbelLanes;
+  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "%s: too many points", what);
+  *grid = (unsigned)g;
+  return use_device(dev);
+}
+
+static int launch_gumbel_cdf(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* x,
+                             uint32_t nx, double freq, int mode, double* out) {
+  if (npts == 0 || nx == 0) return EKM_OK;
+  if (mode != EKM_GUMBEL_CDF && mode != EKM_GUMBEL_RETURN_PERIOD)
+    return set_error(EKM_ERR_ENUM, "gumbel_cdf: mode=%d is not EKM_GUMBEL_CDF or EKM_GUMBEL_RETURN_PERIOD", mode);
+  unsigned grid;
+  int rc = gumbel_prepare(dev, "gumbel_cdf", npts, nx, {mu, sigma, x, out}, &grid);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL(gumbel_cdf_points, dim3(grid), dim3(kGumbelLanes), 0, static_cast<hipStream_t>(stream), mu, sigma,
+                     (unsigned long long)npts, x, nx, freq, mode, out);
+  return ens_launched("gumbel_cdf");
+}
+
+static int launch_gumbel_ppf(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* t,
+                             uint32_t nt, double* out) {
+  if (npts == 0 || nt == 0) return EKM_OK;
+  unsigned grid;
+  int rc = gumbel_prepare(dev, "gumbel_ppf", npts, nt, {mu, sigma, t, out}, &grid);
+  if (rc != EKM_OK) return rc;
+  hipLaunchKernelGGL(gumbel_ppf_points, dim3(grid), dim3(kGumbelLanes), 0, static_cast<hipStream_t>(stream), mu, sigma,
+                     (unsigned long long)npts, t, nt, out);
+  return ens_launched("gumbel_ppf");
+}
+
 }  // namespace ekm
 
 extern "C" {
+
+int ekm_gumbel_fit_f32(int dev, void* stream, const float* sample, size_t outer, uint32_t m, size_t inner, double* mu,
+                       double* sigma) {
+  return ekm::launch_gumbel_fit<float>(dev, stream, sample, outer, m, inner, mu, sigma);
+}
+int ekm_gumbel_fit_f64(int dev, void* stream, const double* sample, size_t outer, uint32_t m, size_t inner, double* mu,
+                       double* sigma) {
+  return ekm::launch_gumbel_fit<double>(dev, stream, sample, outer, m, inner, mu, sigma);
+}
+int ekm_gumbel_cdf_f64(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* x,
+                       uint32_t nx, double freq, int mode, double* out) {
+  return ekm::launch_gumbel_cdf(dev, stream, mu, sigma, npts, x, nx, freq, mode, out);
+}
+int ekm_gumbel_ppf_f64(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* t,
+                       uint32_t nt, double* out) {
+  return ekm::launch_gumbel_ppf(dev, stream, mu, sigma, npts, t, nt, out);
+}
 
 int ekm_quantiles_f32(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner, const double* lo,
                       const double* hi, const double* w, uint32_t nq, int mode, float* out) {

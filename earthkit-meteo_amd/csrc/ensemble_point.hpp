@@ -1,8 +1,8 @@
 // Reductions over the member axis of one grid point: Extreme Forecast Index, Shift of Tails and CRPS of an ensemble
-// against a model climate or an analysis.  One statement of the arithmetic for the gfx950 kernels (ensemble.hip) and
-// the host test twin (host_twin.cpp).
+// against a model climate or an analysis, per-point quantiles, and the Gumbel fit with its cdf and ppf.  One statement
+// of the arithmetic for the gfx950 kernels (ensemble.hip) and the host test twin (host_twin.cpp).
 // Reference: extreme/array/efi.py:34-89, extreme/array/sot.py:13-103, extreme/array/cpf.py:13-155,
-// score/array/ensemble.py:34-82, stats/array/quantiles.py:18-84.
+// score/array/ensemble.py:34-82, stats/array/quantiles.py:18-84, stats/array/extreme_values.py:24-155.
 //
 // All of them work on the point's ensemble SORTED ascending; `s(j)` below reads sorted member j.  The results are held to
 // the reference bit for bit, so every operation is rounded once in the reference's order: nothing is contracted into
@@ -288,5 +288,45 @@ EKM_HD double crps_point(unsigned n, T y, Sorted s, const double* p2, const doub
   }
   return sum;
 }
+
+// extreme_values.py:44-64 (GumbelDistribution.fit) for one point: the first two sample L-moments of the column sorted
+// ascending, formed as the reference's own lmoment (_polyfill.py:30-65) forms them, then sigma = l2 / log(2) and
+// mu = l1 - sigma * 0.5772.  Everything is float64 whatever T is (an f32 sample is widened on read); every operation is
+// rounded once, in the polyfill's order.  The polyfill's third sum is never read by `fit` and is not formed.  Infinities
+// go through the arithmetic as written: a leading -inf gives -inf * 0 = NaN in s1.
+template <class T, class Sorted>
+EKM_HD void gumbel_fit_point(unsigned n, bool col_nan, Sorted s, double& mu, double& sigma) {
+  double s0 = 0.0, s1 = 0.0;
+  for (unsigned i = 0; i < n; ++i) {
+    const double x = (double)s(i);
+    s0 = en_add(s0, x);
+    s1 = en_add(s1, en_mul(x, (double)i));
+  }
+  const double b0 = s0 / (double)n;
+  const double b1 = s1 / en_mul((double)n, (double)(n - 1));
+  const double l2 = en_add(en_mul(-1.0, b0), en_mul(2.0, b1));
+  const double sg = l2 / 0.6931471805599453;  // numpy.log(2)
+  const double m = en_sub(b0, en_mul(sg, 0.5772));
+  mu = col_nan ? nan_v<double>() : m;
+  sigma = col_nan ? nan_v<double>() : sg;
+}
+
+// extreme_values.py:76-92 (cdf) and :113-133 (value_to_return_period) for one point and one level.  `mode` is
+// EKM_GUMBEL_CDF / EKM_GUMBEL_RETURN_PERIOD of include/ekm_thermo.h: the cdf, or freq / cdf by IEEE division, so the
+// return period is freq / cdf formed from the same cdf bit for bit.
+// The exponentials are the platform libm's `exp` (the device library's on gfx950), NOT the project's m_exp: m_exp is
+// built to 4e-11 relative, which is right for the thermo bar, but the subtraction from 1 turns that into 4e-11 ABSOLUTE
+// on the cdf -- a cdf can be 1e-12, and its reciprocal, the return period, is the product the user wants.
+constexpr int kGumbelCdf = 0, kGumbelReturnPeriod = 1;
+EKM_HD double gumbel_cdf_point(double mu, double sigma, double x, double freq, int mode) {
+  const double z = en_sub(mu, x) / sigma;
+  const double c = en_sub(1.0, ::exp(-::exp(z)));
+  return mode == kGumbelReturnPeriod ? freq / c : c;
+}
+
+// extreme_values.py:94-110 (ppf) and :136-155 (return_period_to_value): mu - sigma * t, the product and then the
+// difference, no fma.  t = log(-log(1 - p)) is computed by the host with NumPy exactly as the reference computes it (as
+// for the quantile positions above); no logarithm is evaluated here, so the result is the reference's bit for bit.
+EKM_HD double gumbel_ppf_point(double mu, double sigma, double t) { return en_sub(mu, en_mul(sigma, t)); }
 
 }  // namespace ekm

@@ -299,6 +299,40 @@ EKM_HOST_QUANTILES(f64, double, double)
 EKM_HOST_QUANTILES(f32_f64, float, double)
 #undef EKM_HOST_QUANTILES
 
+// ---- Gumbel fit, cdf and ppf: gumbel_*_point of ensemble_point.hpp on the CPU, same arguments as ekm_gumbel_* without
+// dev / stream (the exponentials are this host's libm, the device library's on the GPU) ----
+template <class T>
+static int host_gumbel_fit(const T* sample, size_t outer, unsigned m, size_t inner, double* mu, double* sigma) {
+  if (outer == 0 || inner == 0) return 0;
+  if (m < 2) return -2;
+  std::vector<T> col(m);
+  for (size_t p = 0; p < outer * inner; ++p) {
+    const size_t o = p / inner, i = p - o * inner;
+    const bool has_nan = host_sort_members<T>(sample + o * m * inner, m, inner, i, col, false, T(0));
+    ekm::gumbel_fit_point<T>(m, has_nan, [&](unsigned j) { return col[j]; }, mu[p], sigma[p]);
+  }
+  return 0;
+}
+extern "C" int ekm_host_gumbel_fit_f32(const float* sample, size_t outer, unsigned m, size_t inner, double* mu, double* sigma) {
+  return host_gumbel_fit<float>(sample, outer, m, inner, mu, sigma);
+}
+extern "C" int ekm_host_gumbel_fit_f64(const double* sample, size_t outer, unsigned m, size_t inner, double* mu, double* sigma) {
+  return host_gumbel_fit<double>(sample, outer, m, inner, mu, sigma);
+}
+extern "C" int ekm_host_gumbel_cdf_f64(const double* mu, const double* sigma, size_t npts, const double* x, unsigned nx,
+                                       double freq, int mode, double* out) {
+  if (mode != ekm::kGumbelCdf && mode != ekm::kGumbelReturnPeriod) return -3;
+  for (unsigned k = 0; k < nx; ++k)
+    for (size_t p = 0; p < npts; ++p) out[(size_t)k * npts + p] = ekm::gumbel_cdf_point(mu[p], sigma[p], x[k], freq, mode);
+  return 0;
+}
+extern "C" int ekm_host_gumbel_ppf_f64(const double* mu, const double* sigma, size_t npts, const double* t, unsigned nt,
+                                       double* out) {
+  for (unsigned k = 0; k < nt; ++k)
+    for (size_t p = 0; p < npts; ++p) out[(size_t)k * npts + p] = ekm::gumbel_ppf_point(mu[p], sigma[p], t[k]);
+  return 0;
+}
+
 // ---- wind: wind_point of wind_point.hpp on the CPU, the operands described as for ekm_wind_* (mode, len, inner); a null
 // output is not written ----
 template <class T, int KIND, int MODE, int WHICH>

@@ -20,6 +20,7 @@ EPT_METHOD = {"ifs": 0, "bolton35": 1, "bolton39": 2}
 T_METHOD = {"bisect": 0, "newton": 1, "direct": 2}
 LCL_METHOD = {"davies": 0, "bolton": 1}
 QUANTILE_SORT, QUANTILE_LERP = 0, 1
+GUMBEL_CDF, GUMBEL_RETURN_PERIOD = 0, 1
 
 
 class EkmError(RuntimeError):
@@ -98,6 +99,9 @@ def _signatures():
         sig[f"ekm_wind_xy_{tag}"] = ([i, vp, op, op, i, vp, vp, sz], i)
         sig[f"ekm_wind_coriolis_{tag}"] = ([i, vp, op, vp, sz], i)
         sig[f"ekm_windrose_{tag}"] = ([i, vp, vp, vp, sz, vp, u32, u32, dbl, i, vp, vp], i)
+        sig[f"ekm_gumbel_fit_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp], i)
+    sig["ekm_gumbel_cdf_f64"] = ([i, vp, vp, vp, sz, vp, u32, C.c_double, i, vp], i)
+    sig["ekm_gumbel_ppf_f64"] = ([i, vp, vp, vp, sz, vp, u32, vp], i)
     for tag in ("f32", "f64", "f32_f64"):
         sig[f"ekm_quantiles_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp, vp, u32, i, vp], i)
         sig[f"ekm_solar_{tag}"] = ([i, vp, C.POINTER(Operand), C.POINTER(Operand), vp, u32, vp, sz], i)

@@ -26,13 +26,37 @@ Limits and deviations:
     numpy.quantile on f64 data (the reference casts each level to the integer dtype, i.e. to 0 or 1).
 The first use of a (method, sample count, levels) uploads its position table, which cannot be recorded: call once outside
 an `ekm_hip.graph()` block before recording.
+
+`GumbelDistribution`, `value_to_return_period` and `return_period_to_value` (reference stats/array/extreme_values.py:24-155;
+kernels `gumbel_fit_points`, `gumbel_cdf_points`, `gumbel_ppf_points` in csrc/ensemble.hip) keep the reference's names,
+argument order and defaults.  `fit` sorts the sample axis of every point in LDS and forms the first two L-moments as the
+reference's own `lmoment` (stats/array/_polyfill.py) forms them; `cdf` and `ppf` are outer products of the levels and the
+points, shape `x.shape + dist.shape`.  `mu` and `sigma` are NumPy arrays for NumPy input, `DeviceArray`s for device input
+and tensors of the caller's library for its device tensors, and so are the results.  `ppf` and `return_period_to_value`
+equal the reference bit for bit (the host forms log(-log(1 - p)) with NumPy, the kernel one product and one difference);
+`fit` equals the reference's polyfill on the sample widened to float64 bit for bit; `cdf` is within 8 * 2**-53 absolute
+of the reference (two exponentials of the device library), and the return period is `freq / cdf` of that cdf.
+
+Deviations of the Gumbel functions:
+  * mu, sigma and every result are float64.  The reference gives f32 when mu, sigma and x are all f32; levels,
+    probabilities and return periods are read as float64 on the host;
+  * the sample axis holds at most 256 values in f32 and 128 in f64; more raises `EkmError`;
+  * samples of 2 and 3 values are accepted in every build.  The reference's polyfill refuses fewer than 4 (SciPy's
+    `lmoment`, which the reference uses where SciPy >= 1.15 is installed, takes 3);
+  * an f32 sample is sorted as f32 and summed in float64.  Both reference paths sum it in f32, so this is the more
+    accurate result: the difference is bounded by 2 n (2**-23 + 2**-52) max|x| per column;
+  * a `timedelta` freq works for NumPy distributions only (the host forms `freq / cdf` and `freq / return_period` as the
+    reference does); for a device distribution it raises `TypeError`.
+The first use of a set of levels uploads it, which cannot be recorded: call once outside an `ekm_hip.graph()` block.
 """
+import datetime
 import math
+import numbers
 
 import numpy as np
 
 from . import _ensemble as _e
-from ._ffi import QUANTILE_LERP, QUANTILE_SORT
+from ._ffi import GUMBEL_CDF, GUMBEL_RETURN_PERIOD, QUANTILE_LERP, QUANTILE_SORT
 from .device import DeviceArray, current_stream
 from .vertical import _foreign_aware
 
@@ -123,3 +147,166 @@ def iter_quantiles(arr, which=100, axis=0, method="sort"):
             yield res.flat_slice(k * n, (k + 1) * n).reshape(res.shape[1:])
     else:
         yield from res
+
+
+def _as_f64_device(a, shape, device):
+    """`a` (DeviceArray or NumPy) as a float64 DeviceArray of `shape`; another dtype or shape goes through the host."""
+    if isinstance(a, DeviceArray) and a.dtype == _F64 and tuple(a.shape) == shape:
+        return a
+    host = a.to_host() if isinstance(a, DeviceArray) else np.asarray(a)
+    return DeviceArray.from_host(np.ascontiguousarray(np.broadcast_to(host.astype(np.float64), shape)), device).reshape(shape)
+
+
+def _is_timedelta(freq):
+    return isinstance(freq, (datetime.timedelta, np.timedelta64))
+
+
+def _numeric_freq(freq):
+    if freq is None:
+        return 1.0
+    if isinstance(freq, (numbers.Real, np.number)) and not isinstance(freq, bool):
+        return float(freq)
+    raise TypeError(f"freq must be None, a number or a timedelta, got {type(freq).__name__}")
+
+
+class GumbelDistribution:
+    """Gumbel distribution for extreme value statistics (extreme_values.py:24-110).
+
+    mu, sigma: offset and scale, numbers or arrays, broadcast against each other and held as float64.
+    freq: None, a number or a timedelta: the duration between the values of the represented data; scales the return
+    periods computed from the distribution."""
+
+    def __init__(self, mu, sigma, freq=None):
+        from . import _engine
+
+        (mu, sigma), self._foreign = _engine._adopt_foreign([mu, sigma])
+        self._handed = None
+        self.freq = freq
+        if _e.on_device(mu, sigma):
+            device = _e.device_of(mu, sigma)
+            shape = np.broadcast_shapes(tuple(np.shape(mu)), tuple(np.shape(sigma)))
+            self._mu, self._sigma = _as_f64_device(mu, shape, device), _as_f64_device(sigma, shape, device)
+        else:
+            mu, sigma = np.broadcast_arrays(np.asarray(mu), np.asarray(sigma))
+            self._mu, self._sigma = mu.astype(np.float64, copy=False), sigma.astype(np.float64, copy=False)
+
+    @classmethod
+    def fit(cls, sample, axis=0, freq=None):
+        """Gumbel distribution with parameters fitted to a sample of values along `axis` by the method of L-moments
+        (extreme_values.py:44-64).  One launch: every point's samples are sorted in LDS, then summed in float64."""
+        from . import _engine
+
+        (sample,), foreign = _engine._adopt_foreign([sample])
+        sample = _e.as_input(sample)
+        shape = tuple(int(v) for v in sample.shape)
+        if not shape:
+            raise ValueError("GumbelDistribution.fit: sample must have at least one dimension")
+        if not -len(shape) <= axis < len(shape):
+            raise np.exceptions.AxisError(axis, len(shape))
+        axis = int(axis) % len(shape)
+        m, outer, inner = shape[axis], math.prod(shape[:axis]), math.prod(shape[axis + 1:])
+        rest = shape[:axis] + shape[axis + 1:]
+        if m < 2:
+            raise ValueError("GumbelDistribution.fit: at least two values are needed along the sample axis")
+        dtype = _e.arith_dtype(sample)
+        if outer * inner == 0 and not _e.on_device(sample):
+            return cls(np.empty(rest), np.empty(rest), freq=freq)  # no work: no device is asked for
+        device, stream, keep = _e.device_of(sample), current_stream(), []
+        mu, sigma = DeviceArray.empty(rest, _F64, device), DeviceArray.empty(rest, _F64, device)
+        if outer * inner:
+            d_sample = _e.upload(sample, dtype, device, stream, keep)
+            _e._ffi.check(getattr(_e.lib(), "ekm_gumbel_fit_" + _e.tag_of(dtype))(
+                device, stream, d_sample.ptr, outer, m, inner, mu.on(stream), sigma.on(stream)))
+        on_device = _e.on_device(sample)
+        dist = cls(_e.finish(mu, on_device), _e.finish(sigma, on_device), freq=freq)
+        dist._foreign = foreign
+        return dist
+
+    def _hand(self):
+        if self._handed is None:
+            from . import _engine
+
+            self._handed = _engine._hand_back((self._mu, self._sigma), self._foreign) if self._foreign else (self._mu, self._sigma)
+        return self._handed
+
+    @property
+    def mu(self):
+        return self._hand()[0]
+
+    @property
+    def sigma(self):
+        return self._hand()[1]
+
+    @property
+    def shape(self):
+        """Tuple of dimensions."""
+        return tuple(self._mu.shape)
+
+    @property
+    def ndim(self):
+        """Number of dimensions."""
+        return len(self._mu.shape)
+
+    @property
+    def _on_device(self):
+        return isinstance(self._mu, DeviceArray)
+
+    def _outer(self, what, levels, freq=1.0, mode=None):
+        """out[k, p] of the `levels` (a float64 array of any shape) and the points: one launch of gumbel_cdf_points
+        (mode given) or gumbel_ppf_points."""
+        levels = np.asarray(levels, dtype=np.float64, order="C")  # (ascontiguousarray would make a number 1-D)
+        shape = tuple(levels.shape) + self.shape
+        npts, nlev = math.prod(self.shape), int(levels.size)
+        if npts == 0 or nlev == 0:
+            res = DeviceArray.empty(shape, _F64, self._mu.device) if self._on_device else np.empty(shape)
+        else:
+            device, stream, keep = _e.device_of(self._mu), current_stream(), []
+            _, (d_levels,) = _e.table(("gumbel", what, levels.tobytes()), nlev, device, lambda: (levels.reshape(-1),))
+            mu, sigma = _e.upload(self._mu, _F64, device, stream, keep), _e.upload(self._sigma, _F64, device, stream, keep)
+            out = DeviceArray.empty(shape, _F64, device)
+            if mode is None:
+                rc = _e.lib().ekm_gumbel_ppf_f64(device, stream, mu.ptr, sigma.ptr, npts, d_levels.on(stream), nlev, out.on(stream))
+            else:
+                rc = _e.lib().ekm_gumbel_cdf_f64(device, stream, mu.ptr, sigma.ptr, npts, d_levels.on(stream), nlev, float(freq),
+                                                 mode, out.on(stream))
+            _e._ffi.check(rc)
+            res = _e.finish(out, self._on_device)
+        if self._foreign:
+            from . import _engine
+
+            res = _engine._hand_back((res,), self._foreign)[0]
+        return res
+
+    def cdf(self, x):
+        """The probability that a random variable from the distribution is less than or equal to x
+        (extreme_values.py:76-92): 1 - exp(-exp((mu - x) / sigma)), shape x.shape + dist.shape."""
+        return self._outer("cdf", x, 1.0, GUMBEL_CDF)
+
+    def ppf(self, p):
+        """The percent point function (inverse cdf) of the probability p in [0, 1] (extreme_values.py:94-110):
+        mu - sigma * log(-log(1 - p)), shape p.shape + dist.shape."""
+        with np.errstate(all="ignore"):
+            t = np.log(-np.log(1.0 - np.asarray(p, dtype=np.float64)))
+        return self._outer("ppf", t)
+
+
+def value_to_return_period(dist, value):
+    """Return period of a value given a distribution of extremes (extreme_values.py:113-133): freq / dist.cdf(value),
+    with freq = 1 when the distribution has none.  A numeric freq is divided in the kernel."""
+    if _is_timedelta(dist.freq):
+        if dist._on_device:
+            raise TypeError("value_to_return_period: a timedelta freq needs a NumPy distribution (the device result is float64)")
+        with np.errstate(all="ignore"):
+            return dist.freq / dist.cdf(value)
+    return dist._outer("return_period", value, _numeric_freq(dist.freq), GUMBEL_RETURN_PERIOD)
+
+
+def return_period_to_value(dist, return_period):
+    """Value for a given return period of a distribution of extremes (extreme_values.py:136-155):
+    dist.ppf(freq / return_period), with freq = 1 when the distribution has none."""
+    if _is_timedelta(dist.freq):
+        if dist._on_device:
+            raise TypeError("return_period_to_value: a timedelta freq needs a NumPy distribution")
+        return dist.ppf(dist.freq / return_period)
+    with np.errstate(all="ignore"):
+        return dist.ppf(_numeric_freq(dist.freq) / np.asarray(return_period, dtype=np.float64))

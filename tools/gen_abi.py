@@ -175,7 +175,8 @@ typedef struct ekm_operand {
  *      Added since, without a bump (an addition breaks no client): the vertical interpolation entry points; the ensemble
  *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*; the per-point quantiles ekm_quantiles_*; the
  *      Crossing Point Forecast ekm_cpf_*; the solar geometry ekm_solar_*; the wind functions
- *      ekm_wind_polar_*, ekm_wind_xy_*, ekm_wind_coriolis_*, ekm_windrose_*. */
+ *      ekm_wind_polar_*, ekm_wind_xy_*, ekm_wind_coriolis_*, ekm_windrose_*; the Gumbel extreme-value fit and its
+ *      functions ekm_gumbel_fit_*, ekm_gumbel_cdf_f64, ekm_gumbel_ppf_f64. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -441,6 +442,34 @@ EKM_API int ekm_quantiles_f64(int dev, void* stream, const double* arr, size_t o
                               const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
 EKM_API int ekm_quantiles_f32_f64(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
                                   const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
+
+/* Gumbel extreme-value statistics: reference stats/array/extreme_values.py:24-155.
+ * ekm_gumbel_fit_*: reference extreme_values.py:44-64 (GumbelDistribution.fit) with the L-moments of
+ *   stats/array/_polyfill.py:14-65.  sample: [outer, m, inner] contiguous as for ekm_quantiles_* (any sample axis);
+ *   2 <= m <= 256 (_f32) / 128 (_f64), more samples return EKM_ERR_ARG.  The column is sorted ascending in LDS, then
+ *   s0 = sum x_i, s1 = sum x_i (i - 1) (i = 1..m, in order), b0 = s0 / m, b1 = s1 / (m (m - 1)), l2 = -b0 + 2 b1,
+ *   sigma = l2 / log(2), mu = b0 - 0.5772 sigma: all in float64 (an f32 sample is widened on read), every operation
+ *   rounded once.  mu, sigma: float64 [outer * inner]; both NaN where the column holds a NaN.
+ * ekm_gumbel_cdf_f64: reference extreme_values.py:76-92 (cdf) and :113-133 (value_to_return_period).
+ *   out[k * npts + p] = c = 1 - exp(-exp((mu[p] - x[k]) / sigma[p])) for mode EKM_GUMBEL_CDF, freq / c (IEEE division of
+ *   that same c) for EKM_GUMBEL_RETURN_PERIOD; plain float64 with the device library's exp.  x: nx levels, float64 on
+ *   the device.
+ * ekm_gumbel_ppf_f64: reference extreme_values.py:94-110 (ppf) and :136-155 (return_period_to_value).
+ *   out[k * npts + p] = mu[p] - sigma[p] * t[k], product and difference rounded once each; t[k] = log(-log(1 - p_k)) is
+ *   computed by the caller as the reference computes it (no logarithm is evaluated here).  t: nt values, float64 on the
+ *   device.
+ * No points or no levels return EKM_OK without a launch.  Only enqueue a kernel: nothing allocates, copies or waits on
+ * the host. */
+#define EKM_GUMBEL_CDF 0
+#define EKM_GUMBEL_RETURN_PERIOD 1
+EKM_API int ekm_gumbel_fit_f32(int dev, void* stream, const float* sample, size_t outer, uint32_t m, size_t inner,
+                               double* mu, double* sigma);
+EKM_API int ekm_gumbel_fit_f64(int dev, void* stream, const double* sample, size_t outer, uint32_t m, size_t inner,
+                               double* mu, double* sigma);
+EKM_API int ekm_gumbel_cdf_f64(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* x,
+                               uint32_t nx, double freq, int mode, double* out);
+EKM_API int ekm_gumbel_ppf_f64(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* t,
+                               uint32_t nt, double* out);
 
 /* ---- solar geometry: cosine of the solar zenith angle, its time average, top-of-atmosphere incident radiation ----
  * Reference solar/array/solar.py:51-96 (cos_solar_zenith_angle), :99-179 (_integrate), :182-254.  One launch, one lane per
