@@ -12,6 +12,7 @@
 #include "ensemble_point.hpp"
 #include "interp_point.hpp"
 #include "ops.hpp"
+#include "reduce_point.hpp"
 #include "solar_point.hpp"
 #include "wind_point.hpp"
 
@@ -411,3 +412,83 @@ extern "C" void ekm_host_atan2_hypot(const double* y, const double* x, double* a
     hy[i] = ekm::wind_hypot(x[i], y[i]);
   }
 }
+
+// ---- the reduce family: project_partial / pearson_point / rows_partial_* of reduce_point.hpp on the CPU, same arguments
+// as ekm_regimes_project_*, ekm_regimes_index_* and ekm_pearson_* without dev / stream.  The workgroup is a loop over
+// its 256 lanes, a wave's butterfly is host_wave_tree over 64 of them: the order of every sum is the kernels' ----
+template <class T, int NP>
+static void host_project_group(const T* field, const T* coef, size_t k, size_t cstride, const T* scale, size_t nfields, T* out) {
+  constexpr int kWaves = ekm::kProjThreads / ekm::kWaveLanes;
+  for (size_t n = 0; n < nfields; ++n) {
+    T lanes[NP][kWaves][ekm::kWaveLanes];
+    for (unsigned t = 0; t < (unsigned)ekm::kProjThreads; ++t) {
+      T acc[NP];
+      ekm::project_partial<T, NP>(field + n * k, coef + n * cstride, k, t, acc);
+      for (int p = 0; p < NP; ++p) lanes[p][t / ekm::kWaveLanes][t % ekm::kWaveLanes] = acc[p];
+    }
+    for (int p = 0; p < NP; ++p) {
+      T part[kWaves];
+      for (int w = 0; w < kWaves; ++w) part[w] = ekm::host_wave_tree<T>(lanes[p][w]);
+      out[(size_t)p * nfields + n] = ekm::project_finish<T>(part, kWaves, scale != nullptr, scale ? scale[n] : T(0));
+    }
+  }
+}
+template <class T>
+static int host_project(const T* field, size_t nfields, size_t k, const T* coef, unsigned npat, size_t cstride, const T* scale, T* out) {
+  if (nfields == 0 || npat == 0) return 0;
+  if (k < 1 || (cstride != 0 && cstride < (size_t)npat * k)) return -2;
+  for (unsigned p0 = 0; p0 < npat; p0 += ekm::kProjGroup) {
+    const T* c = coef + (size_t)p0 * k;
+    T* o = out + (size_t)p0 * nfields;
+    switch (npat - p0 < (unsigned)ekm::kProjGroup ? npat - p0 : (unsigned)ekm::kProjGroup) {
+      case 1: host_project_group<T, 1>(field, c, k, cstride, scale, nfields, o); break;
+      case 2: host_project_group<T, 2>(field, c, k, cstride, scale, nfields, o); break;
+      case 3: host_project_group<T, 3>(field, c, k, cstride, scale, nfields, o); break;
+      case 4: host_project_group<T, 4>(field, c, k, cstride, scale, nfields, o); break;
+      case 5: host_project_group<T, 5>(field, c, k, cstride, scale, nfields, o); break;
+      case 6: host_project_group<T, 6>(field, c, k, cstride, scale, nfields, o); break;
+      case 7: host_project_group<T, 7>(field, c, k, cstride, scale, nfields, o); break;
+      default: host_project_group<T, 8>(field, c, k, cstride, scale, nfields, o); break;
+    }
+  }
+  return 0;
+}
+template <class T>
+static int host_pearson(const T* x, const T* y, size_t outer, size_t m, size_t inner, T* out) {
+  if (outer == 0 || inner == 0) return 0;
+  if (m < 1) return -2;
+  for (size_t p = 0; p < outer * inner; ++p) {
+    if (inner != 1) {
+      const size_t o = p / inner, base = o * m * inner + (p - o * inner);
+      out[p] = ekm::pearson_point<T>(
+          m, [&](size_t i) { return x[base + i * inner]; }, [&](size_t i) { return y[base + i * inner]; });
+      continue;
+    }
+    const T *xr = x + p * m, *yr = y + p * m;
+    T a[ekm::kWaveLanes], b[ekm::kWaveLanes];
+    for (unsigned l = 0; l < (unsigned)ekm::kWaveLanes; ++l) a[l] = ekm::rows_partial_sum<T>(xr, m, l), b[l] = ekm::rows_partial_sum<T>(yr, m, l);
+    const T mx = ekm::host_wave_tree<T>(a) / T(m), my = ekm::host_wave_tree<T>(b) / T(m);
+    for (unsigned l = 0; l < (unsigned)ekm::kWaveLanes; ++l)
+      a[l] = ekm::rows_partial_squares<T>(xr, m, l, mx), b[l] = ekm::rows_partial_squares<T>(yr, m, l, my);
+    const T nx = std::sqrt(ekm::host_wave_tree<T>(a)), ny = std::sqrt(ekm::host_wave_tree<T>(b));
+    for (unsigned l = 0; l < (unsigned)ekm::kWaveLanes; ++l) a[l] = ekm::rows_partial_products<T>(xr, yr, m, l, mx, my, nx, ny);
+    out[p] = ekm::host_wave_tree<T>(a);
+  }
+  return 0;
+}
+#define EKM_HOST_REDUCE(tag, T)                                                                                              \
+  extern "C" int ekm_host_regimes_project_##tag(const T* field, size_t nfields, size_t k, const T* coef, unsigned npat,      \
+                                                size_t coef_stride, const T* scale, T* out) {                                \
+    return host_project<T>(field, nfields, k, coef, npat, coef_stride, scale, out);                                          \
+  }                                                                                                                          \
+  extern "C" int ekm_host_regimes_index_##tag(const T* proj, const T* mean, T mean_value, const T* sd, T sd_value, T* out,   \
+                                                size_t n) {                                                                  \
+    for (size_t i = 0; i < n; ++i) out[i] = ekm::standardise_point<T>(proj[i], mean ? mean[i] : mean_value, sd ? sd[i] : sd_value); \
+    return 0;                                                                                                                \
+  }                                                                                                                          \
+  extern "C" int ekm_host_pearson_##tag(const T* x, const T* y, size_t outer, size_t m, size_t inner, T* out) {              \
+    return host_pearson<T>(x, y, outer, m, inner, out);                                                                      \
+  }
+EKM_HOST_REDUCE(f32, float)
+EKM_HOST_REDUCE(f64, double)
+#undef EKM_HOST_REDUCE

@@ -100,6 +100,9 @@ def _signatures():
         sig[f"ekm_wind_coriolis_{tag}"] = ([i, vp, op, vp, sz], i)
         sig[f"ekm_windrose_{tag}"] = ([i, vp, vp, vp, sz, vp, u32, u32, dbl, i, vp, vp], i)
         sig[f"ekm_gumbel_fit_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp], i)
+        sig[f"ekm_regimes_project_{tag}"] = ([i, vp, vp, sz, sz, vp, u32, sz, vp, vp], i)
+        sig[f"ekm_regimes_index_{tag}"] = ([i, vp, vp, vp, real, vp, real, vp, sz], i)
+        sig[f"ekm_pearson_{tag}"] = ([i, vp, vp, vp, sz, sz, sz, vp], i)
     sig["ekm_gumbel_cdf_f64"] = ([i, vp, vp, vp, sz, vp, u32, C.c_double, i, vp], i)
     sig["ekm_gumbel_ppf_f64"] = ([i, vp, vp, vp, sz, vp, u32, vp], i)
     for tag in ("f32", "f64", "f32_f64"):

@@ -1,4 +1,5 @@
-"""`earthkit.meteo.score.crps_from_ensemble` on MI355X (reference score/array/ensemble.py; kernel csrc/ensemble.hip).
+"""`earthkit.meteo.score` on MI355X: `crps_from_ensemble` (reference score/array/ensemble.py; kernel csrc/ensemble.hip)
+and `pearson_correlation` (reference score/array/deterministic.py; kernels csrc/reduce.hip).
 
 Same name, argument order, default and error conventions as the reference.  NumPy in -> NumPy out; `DeviceArray` in ->
 `DeviceArray` out; device tensors of another ROCm library go through DLPack.  `x` is member-major (n_ens, ...), `y` has
@@ -9,7 +10,21 @@ reference's bit for bit.
 nan_policy: "propagate" leaves NaN at points where x or y holds a NaN.  "raise" and "omit" read the kernel's one-byte
 "missing" flags back to the host, so they wait for the device (and cannot be recorded into a graph); "omit" returns the
 1-D result of the remaining points, compacted on the host also for DeviceArray input (then uploaded again).
+
+`pearson_correlation(x, y, axis=0)`: the correlation of x and y along `axis`, any axis and any length of it (the kernels
+stream the axis; nothing is uploaded but the operands, so the call can be recorded into a graph).  f32 when x and y are
+both f32, otherwise f64 (integers included), the result in that dtype (the reference works in place on x, so for an
+f32 x with an f64 y it returns f32; here that pair is computed and returned in f64).  No NaN policy, as in the
+reference: a NaN in a column, a constant column and a sample axis of length 1 give NaN.  Mean, centring, norms, normalisation and the sum of
+products are formed in the reference's order, in three passes over the samples (2 * 3 * m values read per point):
+  * `axis` is not the last axis with more than one element (inner > 1): one lane per point adds its samples one after
+    the other, which is what NumPy does along such an axis: the result equals the reference's bit for bit;
+  * the samples of a point are contiguous (inner == 1): one wave per point, lane l adds samples l, l + 64, ..., then a
+    fixed butterfly over the lanes.  NumPy adds such rows pairwise, so the bits differ: |got - exact| <= (2 m + 16) eps
+    (tests/_regimes_numpy.py).  The same call gives the same bytes every time.
 """
+import math
+
 import numpy as np
 
 from . import _ensemble as _e
@@ -68,3 +83,36 @@ def crps_from_ensemble(x, y, nan_policy="propagate"):
         return _e.finish(out, device_result)
     res = _e.finish(out, False).reshape(-1)[~missing]
     return DeviceArray.from_host(res, device) if device_result else res
+
+
+@_foreign_aware("x", "y")
+def pearson_correlation(x, y, axis=0):
+    """Pearson correlation coefficient of x and y along `axis` (deterministic.py:13-37).  The shapes must match; the
+    result has x's shape with `axis` removed."""
+    x, y = _e.as_input(x), _e.as_input(y)
+    shape = tuple(int(v) for v in x.shape)
+    if shape != tuple(int(v) for v in y.shape):
+        raise ValueError(f"pearson_correlation: the shapes of x {shape} and y {tuple(y.shape)} must match")
+    if not shape:
+        raise np.exceptions.AxisError(axis, 0)
+    if not -len(shape) <= axis < len(shape):
+        raise np.exceptions.AxisError(axis, len(shape))
+    axis = int(axis) % len(shape)
+    m, outer, inner = shape[axis], math.prod(shape[:axis]), math.prod(shape[axis + 1:])
+    rest = shape[:axis] + shape[axis + 1:]
+    dtype = _e.arith_dtype(x, y)
+    device_result = _e.on_device(x, y)
+    if outer * inner == 0 and not device_result:
+        return np.empty(rest, dtype)  # no work: no device is asked for
+    if m == 0 and not device_result:  # the reference: every array is empty along the axis and the sum of nothing is 0
+        return np.zeros(rest, dtype)[()]
+    device, stream, keep = _e.device_of(x, y), current_stream(), []
+    if m == 0:
+        return DeviceArray.from_host(np.zeros(rest, dtype), device).reshape(rest)
+    out = DeviceArray.empty(rest, dtype, device)
+    if outer * inner == 0:
+        return out
+    d_x, d_y = _e.upload(x, dtype, device, stream, keep), _e.upload(y, dtype, device, stream, keep)
+    _e._ffi.check(getattr(_e.lib(), "ekm_pearson_" + _e.tag_of(dtype))(
+        device, stream, d_x.ptr, d_y.ptr, outer, m, inner, out.on(stream)))
+    return out if device_result else _e.finish(out, False)[()]

@@ -176,7 +176,8 @@ typedef struct ekm_operand {
  *      reductions ekm_efi_*, ekm_sot_*, ekm_sot_func_*, ekm_crps_from_ensemble_*; the per-point quantiles ekm_quantiles_*; the
  *      Crossing Point Forecast ekm_cpf_*; the solar geometry ekm_solar_*; the wind functions
  *      ekm_wind_polar_*, ekm_wind_xy_*, ekm_wind_coriolis_*, ekm_windrose_*; the Gumbel extreme-value fit and its
- *      functions ekm_gumbel_fit_*, ekm_gumbel_cdf_f64, ekm_gumbel_ppf_f64. */
+ *      functions ekm_gumbel_fit_*, ekm_gumbel_cdf_f64, ekm_gumbel_ppf_f64; the reduce family ekm_regimes_project_*,
+ *      ekm_regimes_index_*, ekm_pearson_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -470,6 +471,40 @@ EKM_API int ekm_gumbel_cdf_f64(int dev, void* stream, const double* mu, const do
                                uint32_t nx, double freq, int mode, double* out);
 EKM_API int ekm_gumbel_ppf_f64(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* t,
                                uint32_t nt, double* out);
+
+/* ---- the reduce family: sums along a long axis, streamed, added across lanes in one fixed order ----
+ * ekm_regimes_project_*: reference regimes/array/index.py:10-56 (project).
+ *   out[p * nfields + n] = scale[n] * sum_k field[n * k_len + k] * coef[n * coef_stride + p * k_len + k], p < npat.
+ *   field: [nfields, k] contiguous.  coef: pattern times normalised weight, formed by the caller in the call's dtype;
+ *   coef_stride 0 = the npat rows are shared by all fields ([npat, k]); otherwise every field has its own block of
+ *   npat rows, coef_stride >= npat * k elements apart.  scale: [nfields] (the modulator of ModulatedPatterns), or NULL
+ *   for none.  One workgroup per field; patterns are taken eight at a time, one launch per eight, and the field is read
+ *   once per launch.  Sums are fma chains in the call's dtype (an f32 call accumulates in f32) in a fixed order that
+ *   depends on k alone: the same field gives the same bits at any row index and any element-aligned address, and the
+ *   same call gives the same bytes twice.  k >= 1; pointers aligned to their element.
+ * ekm_regimes_index_*: reference regimes/array/index.py:59-76 (regime_index).
+ *   out[i] = (proj[i] - mean_i) / std_i, the difference rounded once and an IEEE division; mean_i = mean[i], or
+ *   mean_value where mean is NULL, and std likewise.
+ * ekm_pearson_*: reference score/array/deterministic.py:13-37 (pearson_correlation).
+ *   x, y: [outer, m, inner] contiguous (any sample axis), out: [outer * inner]; m >= 1 without a cap.  Mean, centring,
+ *   norms, normalisation and the sum of products in the call's dtype, three passes over the samples.  inner > 1: one
+ *   lane per point adds its samples in order, which is NumPy's order along a non-contiguous axis.  inner == 1: one wave
+ *   per row, lane l adds samples l, l + 64, ..., then a butterfly over the 64 lanes.  NaN where a column holds a NaN,
+ *   is constant, or m == 1.
+ * No fields, no patterns or no points return EKM_OK without a launch.  Only enqueue kernels: nothing allocates, copies
+ * or waits on the host. */
+EKM_API int ekm_regimes_project_f32(int dev, void* stream, const float* field, size_t nfields, size_t k, const float* coef,
+                                    uint32_t npat, size_t coef_stride, const float* scale, float* out);
+EKM_API int ekm_regimes_project_f64(int dev, void* stream, const double* field, size_t nfields, size_t k, const double* coef,
+                                    uint32_t npat, size_t coef_stride, const double* scale, double* out);
+EKM_API int ekm_regimes_index_f32(int dev, void* stream, const float* proj, const float* mean, float mean_value,
+                                  const float* std, float std_value, float* out, size_t n);
+EKM_API int ekm_regimes_index_f64(int dev, void* stream, const double* proj, const double* mean, double mean_value,
+                                  const double* std, double std_value, double* out, size_t n);
+EKM_API int ekm_pearson_f32(int dev, void* stream, const float* x, const float* y, size_t outer, size_t m, size_t inner,
+                            float* out);
+EKM_API int ekm_pearson_f64(int dev, void* stream, const double* x, const double* y, size_t outer, size_t m, size_t inner,
+                            double* out);
 
 /* ---- solar geometry: cosine of the solar zenith angle, its time average, top-of-atmosphere incident radiation ----
  * Reference solar/array/solar.py:51-96 (cos_solar_zenith_angle), :99-179 (_integrate), :182-254.  One launch, one lane per
