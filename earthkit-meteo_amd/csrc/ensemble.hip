@@ -35,16 +35,20 @@
 
 #include "../../include/ekm_thermo.h"
 #include "ensemble_point.hpp"
+#include "launch_checks.hpp"
 #include "map_kernel.hpp"
 
 namespace ekm {
 
 constexpr int kEnsLanes = 64;                   // one wave per workgroup
 constexpr size_t kEnsLdsBytes = 64 * 1024;      // the sorted ensembles of a workgroup
-constexpr int kEnsBatch = 8;                    // member rows in flight per lane while sorting
 
-// Streams the nens members of one point (member j at base[j * stride]) into the lane's LDS column, sorted ascending;
-// returns "a member is NaN".  zero_below: sot.py:88 (members below eps become 0 before the percentile).
+template <class T>
+using LaneColumn = Column<T, kEnsLanes>;  // the lane's column of the workgroup's LDS
+
+// quantile_points and cpf_points keep their earlier bodies and stagers: with the shared ones their instruction streams
+// changed and the timing did not hold (profiles/refactor_launch_ab.json).
+constexpr int kEnsBatch = 8;                    // member rows in flight per lane while sorting
 template <class T>
 __device__ __forceinline__ bool sort_members(const T* __restrict__ base, unsigned long long stride, unsigned nens, T* col,
                                              bool zero_below, T teps) {
@@ -68,6 +72,28 @@ __device__ __forceinline__ bool sort_members(const T* __restrict__ base, unsigne
   return has_nan;
 }
 
+// (cpf) sorted as numpy.sort orders them (NaN last), or as given
+template <class T>
+__device__ __forceinline__ void cpf_stage_column(const T* __restrict__ base, unsigned long long stride, unsigned rows, T* col,
+                                                 bool sort) {
+  auto get = [&](unsigned j) -> T { return col[j * kEnsLanes]; };
+  auto set = [&](unsigned j, T v) { col[j * kEnsLanes] = v; };
+  for (unsigned m0 = 0; m0 < rows; m0 += kEnsBatch) {
+    T v[kEnsBatch];
+#pragma unroll
+    for (int b = 0; b < kEnsBatch; ++b)
+      if (m0 + b < rows) v[b] = base[(unsigned long long)(m0 + b) * stride];
+#pragma unroll
+    for (int b = 0; b < kEnsBatch; ++b)
+      if (m0 + b < rows) {
+        if (sort)
+          ens_insert_nan_last<T>(m0 + b, v[b], get, set);
+        else
+          set(m0 + b, v[b]);
+      }
+  }
+}
+
 template <class T>
 __global__ __launch_bounds__(kEnsLanes) void efi_points(const T* __restrict__ clim, const T* __restrict__ ens,
                                                         unsigned nclim, unsigned nens, unsigned long long npts,
@@ -76,11 +102,8 @@ __global__ __launch_bounds__(kEnsLanes) void efi_points(const T* __restrict__ cl
                                                         const double* __restrict__ acoef, double* __restrict__ out) {
   const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
   if (p >= npts) return;
-  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
-  const bool has_nan = sort_members<T>(ens + p, npts, nens, col, false, T(0));
-  out[p] = efi_point<T>(
-      nclim, nens, has_nan, [&](unsigned i) -> T { return clim[(unsigned long long)i * npts + p]; },
-      [&](unsigned j) -> T { return col[j * kEnsLanes]; }, acosdiff, proddiff, acoef, eps);
+  const LaneColumn<T> col{reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x};
+  efi_body<T>(clim, ens, nclim, nens, npts, p, eps, acosdiff, proddiff, acoef, col, out);
 }
 
 template <class T>
@@ -90,9 +113,8 @@ __global__ __launch_bounds__(kEnsLanes) void sot_points(const T* __restrict__ qc
                                                         T* __restrict__ out) {
   const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
   if (p >= npts) return;
-  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
-  const bool has_nan = sort_members<T>(ens + p, npts, nens, col, eps > 0.0, T(eps));
-  out[p] = sot_point<T>(qc[p], qc_tail[p], has_nan, [&](unsigned j) -> T { return col[j * kEnsLanes]; }, pos, eps);
+  const LaneColumn<T> col{reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x};
+  sot_body<T>(qc, qc_tail, ens, nens, npts, p, pos, eps, col, out);
 }
 
 template <class T>
@@ -102,13 +124,8 @@ __global__ __launch_bounds__(kEnsLanes) void crps_points(const T* __restrict__ x
                                                          unsigned char* __restrict__ missing) {
   const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
   if (p >= npts) return;
-  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
-  const bool has_nan = sort_members<T>(x + p, npts, nens, col, false, T(0));
-  const T yp = y[p];
-  const bool miss = has_nan || yp != yp;  // ensemble.py:44
-  const double r = crps_point<T>(nens, yp, [&](unsigned j) -> T { return col[j * kEnsLanes]; }, p2, q2);
-  out[p] = miss ? nan_v<double>() : r;
-  if (missing) missing[p] = miss ? 1 : 0;
+  const LaneColumn<T> col{reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x};
+  crps_body<T>(x, y, nens, npts, p, p2, q2, col, out, missing);
 }
 
 // quantiles.py:60-84.  arr: [outer, m, inner]; lo, hi, w: the nq position records; out: [nq, npts] in Out.
@@ -139,13 +156,8 @@ __global__ __launch_bounds__(kEnsLanes) void gumbel_fit_points(const T* __restri
                                                                double* __restrict__ mu, double* __restrict__ sigma) {
   const unsigned long long p = (unsigned long long)blockIdx.x * kEnsLanes + threadIdx.x;
   if (p >= npts) return;
-  T* col = reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x;
-  const unsigned long long o = p / inner, i = p - o * inner;
-  const bool has_nan = sort_members<T>(sample + o * m * inner + i, inner, m, col, false, T(0));
-  double mu_p, sigma_p;
-  gumbel_fit_point<T>(m, has_nan, [&](unsigned k) -> T { return col[k * kEnsLanes]; }, mu_p, sigma_p);
-  mu[p] = mu_p;
-  sigma[p] = sigma_p;
+  const LaneColumn<T> col{reinterpret_cast<T*>(ekm_lds_raw) + threadIdx.x};
+  gumbel_fit_body<T>(sample, m, inner, p, col, mu, sigma);
 }
 
 // extreme_values.py:76-110: the outer product of nx levels and npts points, out[k * npts + p].  One lane per point keeps
@@ -173,32 +185,8 @@ __global__ __launch_bounds__(kGumbelLanes) void gumbel_ppf_points(const double* 
   for (unsigned k = 0; k < nt; ++k) out[(unsigned long long)k * npts + p] = gumbel_ppf_point(m, s, t[k]);
 }
 
-// Streams the `rows` values of one point (row j at base[j * stride]) into the lane's LDS column: sorted as numpy.sort
-// orders them (NaN last), or as given.
-template <class T>
-__device__ __forceinline__ void stage_column(const T* __restrict__ base, unsigned long long stride, unsigned rows, T* col,
-                                             bool sort) {
-  auto get = [&](unsigned j) -> T { return col[j * kEnsLanes]; };
-  auto set = [&](unsigned j, T v) { col[j * kEnsLanes] = v; };
-  for (unsigned m0 = 0; m0 < rows; m0 += kEnsBatch) {
-    T v[kEnsBatch];
-#pragma unroll
-    for (int b = 0; b < kEnsBatch; ++b)
-      if (m0 + b < rows) v[b] = base[(unsigned long long)(m0 + b) * stride];
-#pragma unroll
-    for (int b = 0; b < kEnsBatch; ++b)
-      if (m0 + b < rows) {
-        if (sort)
-          ens_insert_nan_last<T>(m0 + b, v[b], get, set);
-        else
-          set(m0 + b, v[b]);
-      }
-  }
-}
-
 // cpf.py:13-155.  KIB: the static LDS of the workgroup; rows [0, nens) hold the ensemble column, rows [nens, nens+nclim)
 // the sorted climate column when sort_clim.
-constexpr unsigned kCpfSortClim = 1, kCpfSortEns = 2, kCpfFromZero = 4, kCpfSymmetric = 8, kCpfEpsilon = 16;
 constexpr size_t kCpfLdsMaxBytes = 160 * 1024;  // the LDS of a gfx950 workgroup
 
 template <class T, int KIB>
@@ -210,12 +198,12 @@ __global__ __launch_bounds__(kEnsLanes) void cpf_points(const T* __restrict__ cl
   if (p >= npts) return;
   T* ecol = lds + threadIdx.x;
   T* ccol = ecol + (size_t)nens * kEnsLanes;
-  stage_column<T>(ens + p, npts, nens, ecol, (flags & kCpfSortEns) != 0);
+  cpf_stage_column<T>(ens + p, npts, nens, ecol, (flags & kCpfSortEns) != 0);
   auto member = [&](unsigned j) -> T { return ecol[j * kEnsLanes]; };
   const bool from_zero = (flags & kCpfFromZero) != 0, symmetric = (flags & kCpfSymmetric) != 0,
              use_eps = (flags & kCpfEpsilon) != 0;
   if (flags & kCpfSortClim) {
-    stage_column<T>(clim + p, npts, nclim, ccol, true);
+    cpf_stage_column<T>(clim + p, npts, nclim, ccol, true);
     out[p] = cpf_value<T>(nclim, nens, from_zero, symmetric, use_eps, epsilon,
                           [&](unsigned i) -> T { return ccol[i * kEnsLanes]; }, member);
   } else {
@@ -233,7 +221,7 @@ __global__ __launch_bounds__(256) void sot_func_points(const T* __restrict__ qc_
   out[p] = sot_func_point<T>(qc_tail[p], qc[p], qf[p], min_den, lower, upper);
 }
 
-// Common argument checks; returns the grid size in *grid
+// What the sorted-column launchers share: the member count against the LDS, the T pointers, the grid, the device
 template <class T>
 static int ens_prepare(int dev, const char* what, size_t npts, uint32_t nens, std::initializer_list<const void*> ptrs,
                        unsigned* grid, size_t* lds) {
@@ -242,21 +230,9 @@ static int ens_prepare(int dev, const char* what, size_t npts, uint32_t nens, st
   if (*lds > kEnsLdsBytes)
     return set_error(EKM_ERR_ARG, "%s: %u members need %zu B of LDS per workgroup (max %zu: %zu members)", what, nens, *lds,
                      kEnsLdsBytes, kEnsLdsBytes / (kEnsLanes * sizeof(T)));
-  for (const void* ptr : ptrs) {
-    if (!ptr) return set_error(EKM_ERR_ARG, "%s: null pointer", what);
-    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(T))
-      return set_error(EKM_ERR_ARG, "%s: a pointer is not aligned to its element size (%d B)", what, (int)sizeof(T));
-  }
-  const unsigned long long g = ((unsigned long long)npts + kEnsLanes - 1) / kEnsLanes;
-  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "%s: too many points", what);
-  *grid = (unsigned)g;
-  return use_device(dev);
-}
-
-static int ens_launched(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
-  return EKM_OK;
+  int rc = check_pointers(what, sizeof(T), ptrs);
+  if (rc == EKM_OK) rc = launch_grid(what, npts, kEnsLanes, grid);
+  return rc == EKM_OK ? use_device(dev) : rc;
 }
 
 template <class T>
@@ -265,14 +241,14 @@ static int launch_efi(int dev, void* stream, const T* clim, const T* ens, uint32
   if (npts == 0) return EKM_OK;
   if (nclim < 1) return set_error(EKM_ERR_ARG, "efi: at least one climate row is required");
   if (nclim > 1 && (!acosdiff || !proddiff || !acoef)) return set_error(EKM_ERR_ARG, "efi: null coefficient table");
-  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(double)) return set_error(EKM_ERR_ARG, "efi: out is null or not 8-B aligned");
+  int rc = check_pointers("efi", sizeof(double), {out});
+  if (rc != EKM_OK) return rc;
   unsigned grid;
   size_t lds;
-  int rc = ens_prepare<T>(dev, "efi", npts, nens, {clim, ens}, &grid, &lds);
-  if (rc != EKM_OK) return rc;
+  if ((rc = ens_prepare<T>(dev, "efi", npts, nens, {clim, ens}, &grid, &lds)) != EKM_OK) return rc;
   hipLaunchKernelGGL((efi_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), clim, ens, nclim,
                      nens, (unsigned long long)npts, eps, acosdiff, proddiff, acoef, out);
-  return ens_launched("efi");
+  return launched("efi");
 }
 
 template <class T>
@@ -286,24 +262,21 @@ static int launch_sot(int dev, void* stream, const T* qc, const T* qc_tail, cons
   if (rc != EKM_OK) return rc;
   hipLaunchKernelGGL((sot_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), qc, qc_tail, ens,
                      nens, (unsigned long long)npts, percentile_position<T>(nens, perc), eps, out);
-  return ens_launched("sot");
+  return launched("sot");
 }
 
 template <class T>
 static int launch_sot_func(int dev, void* stream, const T* qc_tail, const T* qc, const T* qf, size_t n, double eps,
                            double lower, double upper, T* out) {
   if (n == 0) return EKM_OK;
-  for (const void* ptr : {(const void*)qc_tail, (const void*)qc, (const void*)qf, (const void*)out}) {
-    if (!ptr) return set_error(EKM_ERR_ARG, "sot_func: null pointer");
-    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(T)) return set_error(EKM_ERR_ARG, "sot_func: a pointer is not aligned to its element size");
-  }
-  const unsigned long long grid = ((unsigned long long)n + 255) / 256;
-  if (grid > 0x7fffffffull) return set_error(EKM_ERR_ARG, "sot_func: too many points");
-  int rc = use_device(dev);
+  int rc = check_pointers("sot_func", sizeof(T), {qc_tail, qc, qf, out});
+  unsigned grid;
+  if (rc == EKM_OK) rc = launch_grid("sot_func", n, 256, &grid);
+  if (rc == EKM_OK) rc = use_device(dev);
   if (rc != EKM_OK) return rc;
-  hipLaunchKernelGGL((sot_func_points<T>), dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), qc_tail, qc,
-                     qf, (unsigned long long)n, T(eps > 0.0 ? eps : 0.0), T(lower), T(upper), out);
-  return ens_launched("sot_func");
+  hipLaunchKernelGGL((sot_func_points<T>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), qc_tail, qc, qf,
+                     (unsigned long long)n, T(eps > 0.0 ? eps : 0.0), T(lower), T(upper), out);
+  return launched("sot_func");
 }
 
 template <class T, int KIB>
@@ -325,27 +298,22 @@ static int launch_cpf(int dev, void* stream, const T* clim, const T* ens, uint32
     return set_error(EKM_ERR_ARG, "cpf: %u members%s need %zu B of LDS per workgroup (max %zu: %zu rows)", nens,
                      sort_clim ? " and the climate rows to sort" : "", lds, kCpfLdsMaxBytes,
                      kCpfLdsMaxBytes / (kEnsLanes * sizeof(T)));
-  for (const void* ptr : {(const void*)clim, (const void*)ens}) {
-    if (!ptr) return set_error(EKM_ERR_ARG, "cpf: null pointer");
-    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(T))
-      return set_error(EKM_ERR_ARG, "cpf: a pointer is not aligned to its element size (%d B)", (int)sizeof(T));
-  }
-  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(float)) return set_error(EKM_ERR_ARG, "cpf: out is null or not 4-B aligned");
-  const unsigned long long g = ((unsigned long long)npts + kEnsLanes - 1) / kEnsLanes;
-  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "cpf: too many points");
-  int rc = use_device(dev);
+  int rc = check_pointers("cpf", sizeof(T), {clim, ens});
+  if (rc == EKM_OK) rc = check_pointers("cpf", sizeof(float), {out});
+  unsigned g;
+  if (rc == EKM_OK) rc = launch_grid("cpf", npts, kEnsLanes, &g);
+  if (rc == EKM_OK) rc = use_device(dev);
   if (rc != EKM_OK) return rc;
-  const unsigned flags = (sort_clim ? kCpfSortClim : 0) | (sort_ens ? kCpfSortEns : 0) | (from_zero ? kCpfFromZero : 0) |
-                         (symmetric ? kCpfSymmetric : 0) | (use_epsilon && !symmetric ? kCpfEpsilon : 0);
+  const unsigned flags = cpf_flags(sort_clim, sort_ens, from_zero, symmetric, use_epsilon);
   if (lds <= 20 * 1024)
-    launch_cpf_bucket<T, 20>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+    launch_cpf_bucket<T, 20>(g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
   else if (lds <= 40 * 1024)
-    launch_cpf_bucket<T, 40>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+    launch_cpf_bucket<T, 40>(g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
   else if (lds <= 80 * 1024)
-    launch_cpf_bucket<T, 80>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+    launch_cpf_bucket<T, 80>(g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
   else
-    launch_cpf_bucket<T, 160>((unsigned)g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
-  return ens_launched("cpf");
+    launch_cpf_bucket<T, 160>(g, stream, clim, ens, nclim, nens, npts, flags, epsilon, out);
+  return launched("cpf");
 }
 
 template <class T>
@@ -353,15 +321,14 @@ static int launch_crps(int dev, void* stream, const T* x, const T* y, uint32_t n
                        const double* q2, double* out, uint8_t* missing) {
   if (npts == 0) return EKM_OK;
   if (!p2 || !q2) return set_error(EKM_ERR_ARG, "crps_from_ensemble: null weight table");
-  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(double))
-    return set_error(EKM_ERR_ARG, "crps_from_ensemble: out is null or not 8-B aligned");
+  int rc = check_pointers("crps_from_ensemble", sizeof(double), {out});
+  if (rc != EKM_OK) return rc;
   unsigned grid;
   size_t lds;
-  int rc = ens_prepare<T>(dev, "crps_from_ensemble", npts, nens, {x, y}, &grid, &lds);
-  if (rc != EKM_OK) return rc;
+  if ((rc = ens_prepare<T>(dev, "crps_from_ensemble", npts, nens, {x, y}, &grid, &lds)) != EKM_OK) return rc;
   hipLaunchKernelGGL((crps_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), x, y, nens,
                      (unsigned long long)npts, p2, q2, out, missing);
-  return ens_launched("crps_from_ensemble");
+  return launched("crps_from_ensemble");
 }
 
 template <class T, class Out>
@@ -375,15 +342,14 @@ static int launch_quantiles(int dev, void* stream, const T* arr, size_t outer, u
   if (inner > ~(size_t)0 / outer) return set_error(EKM_ERR_ARG, "quantiles: too many points");
   const size_t npts = outer * inner;
   if (!lo || !hi || !w) return set_error(EKM_ERR_ARG, "quantiles: null position table");
-  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(Out))
-    return set_error(EKM_ERR_ARG, "quantiles: out is null or not aligned to its element size (%d B)", (int)sizeof(Out));
+  int rc = check_pointers("quantiles", sizeof(Out), {out});
+  if (rc != EKM_OK) return rc;
   unsigned grid;
   size_t lds;
-  int rc = ens_prepare<T>(dev, "quantiles", npts, m, {arr}, &grid, &lds);
-  if (rc != EKM_OK) return rc;
+  if ((rc = ens_prepare<T>(dev, "quantiles", npts, m, {arr}, &grid, &lds)) != EKM_OK) return rc;
   hipLaunchKernelGGL((quantile_points<T, Out>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), arr, m,
                      (unsigned long long)inner, (unsigned long long)npts, lo, hi, w, nq, mode, out);
-  return ens_launched("quantiles");
+  return launched("quantiles");
 }
 
 template <class T>
@@ -393,30 +359,23 @@ static int launch_gumbel_fit(int dev, void* stream, const T* sample, size_t oute
   if (m < 2) return set_error(EKM_ERR_ARG, "gumbel_fit: at least two samples are required, got %u", m);
   if (inner > ~(size_t)0 / outer) return set_error(EKM_ERR_ARG, "gumbel_fit: too many points");
   const size_t npts = outer * inner;
-  for (const double* ptr : {mu, sigma})
-    if (!ptr || reinterpret_cast<uintptr_t>(ptr) % sizeof(double))
-      return set_error(EKM_ERR_ARG, "gumbel_fit: mu or sigma is null or not 8-B aligned");
+  int rc = check_pointers("gumbel_fit", sizeof(double), {mu, sigma});
+  if (rc != EKM_OK) return rc;
   unsigned grid;
   size_t lds;
-  int rc = ens_prepare<T>(dev, "gumbel_fit", npts, m, {sample}, &grid, &lds);
-  if (rc != EKM_OK) return rc;
+  if ((rc = ens_prepare<T>(dev, "gumbel_fit", npts, m, {sample}, &grid, &lds)) != EKM_OK) return rc;
   hipLaunchKernelGGL((gumbel_fit_points<T>), dim3(grid), dim3(kEnsLanes), lds, static_cast<hipStream_t>(stream), sample, m,
                      (unsigned long long)inner, (unsigned long long)npts, mu, sigma);
-  return ens_launched("gumbel_fit");
+  return launched("gumbel_fit");
 }
 
 // The argument checks the two outer-product entry points share; returns the grid size in *grid
 static int gumbel_prepare(int dev, const char* what, size_t npts, uint32_t nlev, std::initializer_list<const void*> ptrs,
                           unsigned* grid) {
-  for (const void* ptr : ptrs) {
-    if (!ptr) return set_error(EKM_ERR_ARG, "%s: null pointer", what);
-    if (reinterpret_cast<uintptr_t>(ptr) % sizeof(double))
-      return set_error(EKM_ERR_ARG, "%s: a pointer is not 8-B aligned", what);
-  }
+  int rc = check_pointers(what, sizeof(double), ptrs);
+  if (rc != EKM_OK) return rc;
   if (npts > ~(size_t)0 / sizeof(double) / nlev) return set_error(EKM_ERR_ARG, "%s: too many points", what);
-  const unsigned long long g = ((unsigned long long)npts + kGumbelLanes - 1) / kGumbelLanes;
-  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "%s: too many points", what);
-  *grid = (unsigned)g;
+  if ((rc = launch_grid(what, npts, kGumbelLanes, grid)) != EKM_OK) return rc;
   return use_device(dev);
 }
 
@@ -430,7 +389,7 @@ static int launch_gumbel_cdf(int dev, void* stream, const double* mu, const doub
   if (rc != EKM_OK) return rc;
   hipLaunchKernelGGL(gumbel_cdf_points, dim3(grid), dim3(kGumbelLanes), 0, static_cast<hipStream_t>(stream), mu, sigma,
                      (unsigned long long)npts, x, nx, freq, mode, out);
-  return ens_launched("gumbel_cdf");
+  return launched("gumbel_cdf");
 }
 
 static int launch_gumbel_ppf(int dev, void* stream, const double* mu, const double* sigma, size_t npts, const double* t,
@@ -441,7 +400,7 @@ static int launch_gumbel_ppf(int dev, void* stream, const double* mu, const doub
   if (rc != EKM_OK) return rc;
   hipLaunchKernelGGL(gumbel_ppf_points, dim3(grid), dim3(kGumbelLanes), 0, static_cast<hipStream_t>(stream), mu, sigma,
                      (unsigned long long)npts, t, nt, out);
-  return ens_launched("gumbel_ppf");
+  return launched("gumbel_ppf");
 }
 
 }  // namespace ekm

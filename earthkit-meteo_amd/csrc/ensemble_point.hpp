@@ -71,6 +71,50 @@ EKM_HD void ens_insert_nan_last(unsigned k, T v, Get get, Set set) {
   set(j, v);
 }
 
+// A point's column of rows, row j at ptr[j * STRIDE]: the lane's LDS column in the kernels (STRIDE 64, lane-minor), a
+// plain array in the host twin (STRIDE 1).  Reads as the `s(j)` of the routines below.
+template <class T, unsigned STRIDE>
+struct Column {
+  T* ptr;
+  EKM_HD T operator()(unsigned j) const { return ptr[j * STRIDE]; }
+  EKM_HD void set(unsigned j, T v) const { ptr[j * STRIDE] = v; }
+};
+
+// Streams the `rows` values of one point (row j at base[j * stride]) into its column, kStageBatch loads in flight.
+//  * Ascending: ens_insert; returns "a value is NaN".  zero_below: sot.py:88 (values below teps become 0 first).
+//  * NanLast: as numpy.sort orders them (ens_insert_nan_last).  AsGiven: copied.
+enum class ColumnOrder { Ascending, NanLast, AsGiven };
+constexpr int kStageBatch = 8;
+
+template <class T, ColumnOrder ORDER, class Col>
+EKM_HD bool stage_column(const T* __restrict__ base, unsigned long long stride, unsigned rows, Col col,
+                         bool zero_below = false, T teps = T(0)) {
+  auto get = [&](unsigned j) -> T { return col(j); };
+  auto set = [&](unsigned j, T v) { col.set(j, v); };
+  bool has_nan = false;
+  for (unsigned m0 = 0; m0 < rows; m0 += kStageBatch) {
+    T v[kStageBatch];
+#pragma unroll
+    for (int b = 0; b < kStageBatch; ++b)
+      if (m0 + b < rows) v[b] = base[(unsigned long long)(m0 + b) * stride];
+#pragma unroll
+    for (int b = 0; b < kStageBatch; ++b)
+      if (m0 + b < rows) {
+        if constexpr (ORDER == ColumnOrder::Ascending) {
+          T x = v[b];
+          if (zero_below && x < teps) x = T(0);
+          has_nan = has_nan || x != x;
+          ens_insert<T>(m0 + b, x, get, set);
+        } else if constexpr (ORDER == ColumnOrder::NanLast) {
+          ens_insert_nan_last<T>(m0 + b, v[b], get, set);
+        } else {
+          set(m0 + b, v[b]);
+        }
+      }
+  }
+  return has_nan;
+}
+
 // efi.py:40-89.  clim(i) is row i of the point's climate, read ONCE each, in order; it need not be sorted: the count
 // of members <= clim(i) (efi.py:49) is the upper-bound rank in the sorted ensemble, found by a cursor that walks either
 // way from the previous row's rank.  frac and dFdp are formed in T (zeros_like(clim), efi.py:46, 51, 55), the terms and
@@ -328,5 +372,65 @@ EKM_HD double gumbel_cdf_point(double mu, double sigma, double x, double freq, i
 // difference, no fma.  t = log(-log(1 - p)) is computed by the host with NumPy exactly as the reference computes it (as
 // for the quantile positions above); no logarithm is evaluated here, so the result is the reference's bit for bit.
 EKM_HD double gumbel_ppf_point(double mu, double sigma, double t) { return en_sub(mu, en_mul(sigma, t)); }
+
+// ---- one point p of a sorted-column kernel of ensemble.hip; the host twin loops over the same.  Fields: [rows, npts] ----
+
+template <class T, class Col>
+EKM_HD void efi_body(const T* clim, const T* ens, unsigned nclim, unsigned nens,
+                     unsigned long long npts, unsigned long long p, double eps, const double* acosdiff,
+                     const double* proddiff, const double* acoef, Col col,
+                     double* out) {
+  const bool has_nan = stage_column<T, ColumnOrder::Ascending>(ens + p, npts, nens, col);
+  out[p] = efi_point<T>(
+      nclim, nens, has_nan, [&](unsigned i) -> T { return clim[(unsigned long long)i * npts + p]; }, col, acosdiff,
+      proddiff, acoef, eps);
+}
+
+template <class T, class Col>
+EKM_HD void sot_body(const T* qc, const T* qc_tail, const T* ens, unsigned nens,
+                     unsigned long long npts, unsigned long long p, Percentile<T> pos, double eps, Col col,
+                     T* out) {
+  const bool has_nan = stage_column<T, ColumnOrder::Ascending>(ens + p, npts, nens, col, eps > 0.0, T(eps));
+  out[p] = sot_point<T>(qc[p], qc_tail[p], has_nan, col, pos, eps);
+}
+
+// missing: one flag byte per point, or null
+template <class T, class Col>
+EKM_HD void crps_body(const T* x, const T* y, unsigned nens, unsigned long long npts,
+                      unsigned long long p, const double* p2, const double* q2, Col col,
+                      double* out, unsigned char* missing) {
+  const bool has_nan = stage_column<T, ColumnOrder::Ascending>(x + p, npts, nens, col);
+  const T yp = y[p];
+  const bool miss = has_nan || yp != yp;  // ensemble.py:44
+  const double r = crps_point<T>(nens, yp, col, p2, q2);
+  out[p] = miss ? nan_v<double>() : r;
+  if (missing) missing[p] = miss ? 1 : 0;
+}
+
+// arr: [outer, m, inner]; the column of point p = o * inner + i starts here and has stride `inner`
+template <class T>
+EKM_HD const T* sample_column(const T* arr, unsigned m, unsigned long long inner, unsigned long long p) {
+  const unsigned long long o = p / inner, i = p - o * inner;
+  return arr + o * m * inner + i;
+}
+
+// extreme_values.py:44-64.  mu, sigma: float64 [npts].
+template <class T, class Col>
+EKM_HD void gumbel_fit_body(const T* sample, unsigned m, unsigned long long inner, unsigned long long p,
+                            Col col, double* mu, double* sigma) {
+  const bool has_nan = stage_column<T, ColumnOrder::Ascending>(sample_column<T>(sample, m, inner, p), inner, m, col);
+  double mu_p, sigma_p;
+  gumbel_fit_point<T>(m, has_nan, col, mu_p, sigma_p);
+  mu[p] = mu_p;
+  sigma[p] = sigma_p;
+}
+
+// cpf.py:13-155: what cpf_points of ensemble.hip reads in its `flags`
+constexpr unsigned kCpfSortClim = 1, kCpfSortEns = 2, kCpfFromZero = 4, kCpfSymmetric = 8, kCpfEpsilon = 16;
+
+inline unsigned cpf_flags(int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon) {
+  return (sort_clim ? kCpfSortClim : 0) | (sort_ens ? kCpfSortEns : 0) | (from_zero ? kCpfFromZero : 0) |
+         (symmetric ? kCpfSymmetric : 0) | (use_epsilon && !symmetric ? kCpfEpsilon : 0);
+}
 
 }  // namespace ekm

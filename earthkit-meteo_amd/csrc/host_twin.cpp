@@ -12,6 +12,7 @@
 #include "ensemble_point.hpp"
 #include "interp_point.hpp"
 #include "ops.hpp"
+#include "point_operand.hpp"
 #include "reduce_point.hpp"
 #include "solar_point.hpp"
 #include "wind_point.hpp"
@@ -146,17 +147,9 @@ EKM_HOST_INTERP(f64, double)
 
 // ---- ensemble reductions: the per-point routines of ensemble.hip (ensemble_point.hpp) on the CPU, same arguments as
 // the ekm_efi_* / ekm_sot_* / ekm_sot_func_* / ekm_crps_from_ensemble_* entry points without dev / stream ----
+// A point's column on the host: a plain array
 template <class T>
-static bool host_sort_members(const T* ens, unsigned nens, size_t npts, size_t p, std::vector<T>& col, bool zero_below, T teps) {
-  bool has_nan = false;
-  for (unsigned m = 0; m < nens; ++m) {
-    T x = ens[(size_t)m * npts + p];
-    if (zero_below && x < teps) x = T(0);
-    has_nan = has_nan || x != x;
-    ekm::ens_insert<T>(m, x, [&](unsigned j) { return col[j]; }, [&](unsigned j, T v) { col[j] = v; });
-  }
-  return has_nan;
-}
+using HostColumn = ekm::Column<T, 1>;
 
 #define EKM_HOST_ENSEMBLE(tag, T)                                                                                    \
   extern "C" int ekm_host_efi_##tag(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts,         \
@@ -164,12 +157,8 @@ static bool host_sort_members(const T* ens, unsigned nens, size_t npts, size_t p
                                     double* out) {                                                                   \
     if (nclim < 1 || nens < 1) return -2;                                                                            \
     std::vector<T> col(nens);                                                                                        \
-    for (size_t p = 0; p < npts; ++p) {                                                                              \
-      const bool has_nan = host_sort_members<T>(ens, nens, npts, p, col, false, T(0));                               \
-      out[p] = ekm::efi_point<T>(                                                                                    \
-          nclim, nens, has_nan, [&](unsigned i) { return clim[(size_t)i * npts + p]; },                              \
-          [&](unsigned j) { return col[j]; }, acosdiff, proddiff, acoef, eps);                                       \
-    }                                                                                                                \
+    for (size_t p = 0; p < npts; ++p)                                                                                \
+      ekm::efi_body<T>(clim, ens, nclim, nens, npts, p, eps, acosdiff, proddiff, acoef, HostColumn<T>{col.data()}, out); \
     return 0;                                                                                                        \
   }                                                                                                                  \
   extern "C" int ekm_host_sot_##tag(const T* qc, const T* qc_tail, const T* ens, unsigned nens, size_t npts,         \
@@ -177,10 +166,8 @@ static bool host_sort_members(const T* ens, unsigned nens, size_t npts, size_t p
     if (nens < 1 || perc < 2 || perc > 98 || perc == 50) return -2;                                                  \
     std::vector<T> col(nens);                                                                                        \
     const ekm::Percentile<T> pos = ekm::percentile_position<T>(nens, perc);                                          \
-    for (size_t p = 0; p < npts; ++p) {                                                                              \
-      const bool has_nan = host_sort_members<T>(ens, nens, npts, p, col, eps > 0.0, T(eps));                         \
-      out[p] = ekm::sot_point<T>(qc[p], qc_tail[p], has_nan, [&](unsigned j) { return col[j]; }, pos, eps);          \
-    }                                                                                                                \
+    for (size_t p = 0; p < npts; ++p)                                                                                \
+      ekm::sot_body<T>(qc, qc_tail, ens, nens, npts, p, pos, eps, HostColumn<T>{col.data()}, out);                   \
     return 0;                                                                                                        \
   }                                                                                                                  \
   extern "C" int ekm_host_sot_func_##tag(const T* qc_tail, const T* qc, const T* qf, size_t n, double eps,           \
@@ -195,13 +182,8 @@ static bool host_sort_members(const T* ens, unsigned nens, size_t npts, size_t p
                                                    unsigned char* missing) {                                         \
     if (nens < 1) return -2;                                                                                         \
     std::vector<T> col(nens);                                                                                        \
-    for (size_t p = 0; p < npts; ++p) {                                                                              \
-      const bool has_nan = host_sort_members<T>(x, nens, npts, p, col, false, T(0));                                 \
-      const bool miss = has_nan || y[p] != y[p];                                                                     \
-      const double r = ekm::crps_point<T>(nens, y[p], [&](unsigned j) { return col[j]; }, p2, q2);                   \
-      out[p] = miss ? ekm::nan_v<double>() : r;                                                                      \
-      if (missing) missing[p] = miss ? 1 : 0;                                                                        \
-    }                                                                                                                \
+    for (size_t p = 0; p < npts; ++p)                                                                                \
+      ekm::crps_body<T>(x, y, nens, npts, p, p2, q2, HostColumn<T>{col.data()}, out, missing);                       \
     return 0;                                                                                                        \
   }
 EKM_HOST_ENSEMBLE(f32, float)
@@ -210,27 +192,17 @@ EKM_HOST_ENSEMBLE(f64, double)
 
 // ---- cpf: cpf_value of ensemble_point.hpp on the CPU, same arguments as ekm_cpf_* without dev / stream ----
 template <class T>
-static void host_stage_column(const T* field, unsigned rows, size_t npts, size_t p, std::vector<T>& col, bool sort) {
-  for (unsigned m = 0; m < rows; ++m) {
-    const T x = field[(size_t)m * npts + p];
-    if (sort)
-      ekm::ens_insert_nan_last<T>(m, x, [&](unsigned j) { return col[j]; }, [&](unsigned j, T v) { col[j] = v; });
-    else
-      col[m] = x;
-  }
-}
-
-template <class T>
 static int host_cpf(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts, int sort_clim, int sort_ens,
                     int from_zero, int symmetric, int use_epsilon, double epsilon, float* out) {
   if (nclim < 1 || nens < 1) return -2;
   std::vector<T> ccol(nclim), ecol(nens);
-  for (size_t p = 0; p < npts; ++p) {
-    host_stage_column<T>(clim, nclim, npts, p, ccol, sort_clim != 0);
-    host_stage_column<T>(ens, nens, npts, p, ecol, sort_ens != 0);
-    out[p] = ekm::cpf_value<T>(
-        nclim, nens, from_zero != 0, symmetric != 0, use_epsilon != 0, T(epsilon), [&](unsigned i) { return ccol[i]; },
-        [&](unsigned j) { return ecol[j]; });
+  const HostColumn<T> cc{ccol.data()}, ec{ecol.data()};
+  for (size_t p = 0; p < npts; ++p) {  // (cpf_points keeps a body of its own: this is its restatement)
+    if (sort_clim) ekm::stage_column<T, ekm::ColumnOrder::NanLast>(clim + p, npts, nclim, cc);
+    else ekm::stage_column<T, ekm::ColumnOrder::AsGiven>(clim + p, npts, nclim, cc);
+    if (sort_ens) ekm::stage_column<T, ekm::ColumnOrder::NanLast>(ens + p, npts, nens, ec);
+    else ekm::stage_column<T, ekm::ColumnOrder::AsGiven>(ens + p, npts, nens, ec);
+    out[p] = ekm::cpf_value<T>(nclim, nens, from_zero != 0, symmetric != 0, use_epsilon != 0, T(epsilon), cc, ec);
   }
   return 0;
 }
@@ -250,10 +222,10 @@ template <class T, class Out>
 static int host_solar(const T* lat, int lat_mode, unsigned long long lat_len, unsigned long long lat_inner, const T* lon,
                       int lon_mode, unsigned long long lon_len, unsigned long long lon_inner, const double* nodes,
                       unsigned nnodes, Out* out, size_t n) {
-  const ekm::SolarOperand<T> la{lat, lat_mode, lat_len ? lat_len : 1, lat_inner ? lat_inner : 1};
-  const ekm::SolarOperand<T> lo{lon, lon_mode, lon_len ? lon_len : 1, lon_inner ? lon_inner : 1};
+  const ekm::PointOperand<T> la{lat, lat_mode, lat_len ? lat_len : 1, lat_inner ? lat_inner : 1};
+  const ekm::PointOperand<T> lo{lon, lon_mode, lon_len ? lon_len : 1, lon_inner ? lon_inner : 1};
   for (size_t p = 0; p < n; ++p)
-    out[p] = ekm::solar_point<Out>(ekm::solar_fetch<T>(la, p, false), ekm::solar_fetch<T>(lo, p, false), nnodes,
+    out[p] = ekm::solar_point<Out>(ekm::point_fetch<T>(la, p, false), ekm::point_fetch<T>(lo, p, false), nnodes,
                                    [&](unsigned k, int j) { return nodes[(size_t)k * ekm::kSolarRecord + j]; });
   return 0;
 }
@@ -281,12 +253,11 @@ static int host_quantiles(const T* arr, size_t outer, unsigned m, size_t inner, 
   if (m < 1 || (mode == ekm::kQuantileSort && sizeof(Out) != sizeof(double))) return -2;
   const size_t npts = outer * inner;
   std::vector<T> col(m);
-  for (size_t p = 0; p < npts; ++p) {
-    const size_t o = p / inner, i = p - o * inner;
-    const bool has_nan = host_sort_members<T>(arr + o * m * inner, m, inner, i, col, false, T(0));
+  const HostColumn<T> c{col.data()};
+  for (size_t p = 0; p < npts; ++p) {  // (quantile_points keeps a body of its own: this is its restatement)
+    const bool has_nan = ekm::stage_column<T, ekm::ColumnOrder::Ascending>(ekm::sample_column<T>(arr, m, inner, p), inner, m, c);
     for (unsigned k = 0; k < nq; ++k)
-      out[(size_t)k * npts + p] = ekm::quantile_point<T, Out>(has_nan, [&](unsigned j) { return col[j]; }, (unsigned)lo[k],
-                                                             (unsigned)hi[k], w[k], mode);
+      out[(size_t)k * npts + p] = ekm::quantile_point<T, Out>(has_nan, c, (unsigned)lo[k], (unsigned)hi[k], w[k], mode);
   }
   return 0;
 }
@@ -307,11 +278,8 @@ static int host_gumbel_fit(const T* sample, size_t outer, unsigned m, size_t inn
   if (outer == 0 || inner == 0) return 0;
   if (m < 2) return -2;
   std::vector<T> col(m);
-  for (size_t p = 0; p < outer * inner; ++p) {
-    const size_t o = p / inner, i = p - o * inner;
-    const bool has_nan = host_sort_members<T>(sample + o * m * inner, m, inner, i, col, false, T(0));
-    ekm::gumbel_fit_point<T>(m, has_nan, [&](unsigned j) { return col[j]; }, mu[p], sigma[p]);
-  }
+  for (size_t p = 0; p < outer * inner; ++p)
+    ekm::gumbel_fit_body<T>(sample, m, inner, p, HostColumn<T>{col.data()}, mu, sigma);
   return 0;
 }
 extern "C" int ekm_host_gumbel_fit_f32(const float* sample, size_t outer, unsigned m, size_t inner, double* mu, double* sigma) {
@@ -337,11 +305,11 @@ extern "C" int ekm_host_gumbel_ppf_f64(const double* mu, const double* sigma, si
 // ---- wind: wind_point of wind_point.hpp on the CPU, the operands described as for ekm_wind_* (mode, len, inner); a null
 // output is not written ----
 template <class T, int KIND, int MODE, int WHICH>
-static void host_wind_as(const ekm::SolarOperand<T>& a, const ekm::SolarOperand<T>& b, T* out0, T* out1, size_t n) {
+static void host_wind_as(const ekm::PointOperand<T>& a, const ekm::PointOperand<T>& b, T* out0, T* out1, size_t n) {
   for (size_t p = 0; p < n; ++p) {
     T o0, o1;
-    ekm::wind_point<T, KIND, MODE, WHICH>((T)ekm::solar_fetch<T>(a, p, false),
-                                          KIND == ekm::WIND_KIND_CORIOLIS ? T(0) : (T)ekm::solar_fetch<T>(b, p, false), o0, o1);
+    ekm::wind_point<T, KIND, MODE, WHICH>((T)ekm::point_fetch<T>(a, p, false),
+                                          KIND == ekm::WIND_KIND_CORIOLIS ? T(0) : (T)ekm::point_fetch<T>(b, p, false), o0, o1);
     if (out0) out0[p] = (T)o0;
     if (out1) out1[p] = (T)o1;
   }
@@ -349,8 +317,8 @@ static void host_wind_as(const ekm::SolarOperand<T>& a, const ekm::SolarOperand<
 template <class T>
 static int host_wind(int kind, const T* a, int a_mode, unsigned long long a_len, unsigned long long a_inner, const T* b, int b_mode,
                      unsigned long long b_len, unsigned long long b_inner, int mode, T* out0, T* out1, size_t n) {
-  const ekm::SolarOperand<T> oa{a, a_mode, a_len ? a_len : 1, a_inner ? a_inner : 1};
-  const ekm::SolarOperand<T> ob{b ? b : a, b ? b_mode : a_mode, b_len ? b_len : 1, b_inner ? b_inner : 1};
+  const ekm::PointOperand<T> oa{a, a_mode, a_len ? a_len : 1, a_inner ? a_inner : 1};
+  const ekm::PointOperand<T> ob{b ? b : a, b ? b_mode : a_mode, b_len ? b_len : 1, b_inner ? b_inner : 1};
   using namespace ekm;
   if (kind == WIND_KIND_POLAR && mode == WIND_METEO) host_wind_as<T, WIND_KIND_POLAR, WIND_METEO, 3>(oa, ob, out0, out1, n);
   else if (kind == WIND_KIND_POLAR && mode == WIND_POLAR_POSITIVE) host_wind_as<T, WIND_KIND_POLAR, WIND_POLAR_POSITIVE, 3>(oa, ob, out0, out1, n);

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "../../include/ekm_thermo.h"
+#include "launch_checks.hpp"
 #include "map_kernel.hpp"
 
 namespace ekm {
@@ -351,16 +352,15 @@ static int launch_geopotential(int dev, void* stream, const T* A, const T* B, co
   for (const void* ptr : {(const void*)sp, (const void*)zs, (const void*)t, (const void*)q, (const void*)out,
                           (const void*)alpha_in, (const void*)delta_in})
     if (ptr && reinterpret_cast<uintptr_t>(ptr) % sizeof(T)) vec_ok = 0;
-  const unsigned long long nchunk = (npts + V - 1) / V;
-  const unsigned long long grid = (nchunk + kGeoThreads - 1) / kGeoThreads;
-  if (grid > 0x7fffffffull) return set_error(EKM_ERR_ARG, "geopotential_on_hybrid_levels: too many columns");
+  unsigned grid;  // workgroups of kGeoThreads lanes, V columns per lane
+  if ((rc = launch_grid("geopotential_on_hybrid_levels", npts, kGeoThreads * V, &grid)) != EKM_OK) return rc;
   // chunks of at most `geo_chunk_levels` levels, balanced, launched from the surface upward on the same stream
   const unsigned maxc = (unsigned)tuning_geo_chunk_levels();
   const unsigned nchunks = (nfull + maxc - 1) / maxc;
   for (unsigned c = 0; c < nchunks; ++c) {
     const unsigned k_hi = nfull - (unsigned)((unsigned long long)nfull * c / nchunks);
     const unsigned k_lo = nfull - (unsigned)((unsigned long long)nfull * (c + 1) / nchunks);
-    const dim3 g((unsigned)grid), b(kGeoThreads);
+    const dim3 g(grid), b(kGeoThreads);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned long long np_ = npts;
 #define EKM_GEO_LAUNCH(VEC_, AD_)                                                                                   \
@@ -373,9 +373,7 @@ static int launch_geopotential(int dev, void* stream, const T* A, const T* B, co
     }
 #undef EKM_GEO_LAUNCH
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "geopotential_columns launch: %s", hipGetErrorString(e));
-  return EKM_OK;
+  return launched("geopotential_on_hybrid_levels");
 }
 
 template <class T>
@@ -391,9 +389,8 @@ static int launch_hybrid(int dev, void* stream, const T* A, const T* B, const T*
   int vec_ok = (npts % V == 0) && reinterpret_cast<uintptr_t>(sp) % sizeof(T) == 0;
   for (T* o : {full, half, delta, alpha})
     if (o && reinterpret_cast<uintptr_t>(o) % sizeof(T)) vec_ok = 0;
-  const unsigned long long nchunk = (npts + V - 1) / V;
-  const unsigned long long grid = (nchunk + kThreads - 1) / kThreads;
-  if (grid > 0x7fffffffull) return set_error(EKM_ERR_ARG, "pressure_on_hybrid_levels: too many columns");
+  unsigned grid;  // workgroups of kThreads lanes, V columns per lane
+  if ((rc = launch_grid("pressure_on_hybrid_levels", npts, kThreads * V, &grid)) != EKM_OK) return rc;
   const unsigned rows = nfull + (half ? 1u : 0u);
   if (tuning_hybrid_rows() && rows <= 65535u) {
     unsigned long long band = (unsigned long long)tuning_hybrid_band_bytes() / ((unsigned long long)kThreads * V * sizeof(T));
@@ -404,13 +401,11 @@ static int launch_hybrid(int dev, void* stream, const T* A, const T* B, const T*
                        static_cast<hipStream_t>(stream), A, B, sp, (unsigned long long)npts, nfull, row_full, row_half,
                        top_is_zero, alpha_top, full, half, delta, alpha, vec_ok);
   } else {
-    hipLaunchKernelGGL((hybrid_levels<T>), dim3((unsigned)grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), A,
+    hipLaunchKernelGGL((hybrid_levels<T>), dim3(grid), dim3(kThreads), 0, static_cast<hipStream_t>(stream), A,
                        B, sp, (unsigned long long)npts, nfull, row_full, row_half, top_is_zero, alpha_top, full, half,
                        delta, alpha, vec_ok);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "hybrid_levels launch: %s", hipGetErrorString(e));
-  return EKM_OK;
+  return launched("pressure_on_hybrid_levels");
 }
 
 template <class T>
@@ -424,9 +419,7 @@ static int launch_any_le(int dev, void* stream, const T* sp, size_t n, T a0, T b
   if (want == 0) want = 1;
   hipLaunchKernelGGL((any_le<T>), dim3((unsigned)(want < cap ? want : cap)), dim3(kThreads), 0,
                      static_cast<hipStream_t>(stream), sp, (unsigned long long)n, a0, b0, thresh, flag);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "any_le launch: %s", hipGetErrorString(e));
-  return EKM_OK;
+  return launched("any_le");
 }
 
 }  // namespace ekm

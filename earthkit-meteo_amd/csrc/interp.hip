@@ -20,6 +20,7 @@
 
 #include "../../include/ekm_thermo.h"
 #include "interp_point.hpp"
+#include "launch_checks.hpp"
 #include "map_kernel.hpp"
 
 namespace ekm {
@@ -158,13 +159,10 @@ static int launch_interp(int dev, void* stream, InterpArgs<T> a, uint32_t ntarge
   if (rc != EKM_OK) return rc;
   constexpr int V = VecOf<T>::N;
   a.vec_ok = (a.npts % V == 0);  // rows of data / target / out start at multiples of npts elements
-  const void* ptrs[] = {a.data, a.coord, a.sp, a.target, a.out, a.aux[0], a.aux[1], a.aux[2], a.aux[3]};
-  for (const void* ptr : ptrs)
-    if (ptr && reinterpret_cast<uintptr_t>(ptr) % sizeof(T))
-      return set_error(EKM_ERR_ARG, "%s: a pointer is not aligned to its element size (%d B)", what, (int)sizeof(T));
-  const unsigned long long nchunk = (a.npts + V - 1) / V;
-  const unsigned long long grid = (nchunk + kThreads - 1) / kThreads;
-  if (grid > 0x7fffffffull) return set_error(EKM_ERR_ARG, "%s: too many columns", what);
+  rc = check_aligned_if_given(what, sizeof(T), {a.data, a.coord, a.sp, a.target, a.out, a.aux[0], a.aux[1], a.aux[2], a.aux[3]});
+  unsigned grid;  // workgroups of kThreads lanes, V columns per lane
+  if (rc == EKM_OK) rc = launch_grid(what, a.npts, kThreads * V, &grid);
+  if (rc != EKM_OK) return rc;
   // bands of surface pressure / columns, every target of a band before the next band (hybrid_rows does the same)
   unsigned long long band = (unsigned long long)tuning_hybrid_band_bytes() / ((unsigned long long)kThreads * V * sizeof(T));
   if (band < 8) band = 8;
@@ -172,9 +170,7 @@ static int launch_interp(int dev, void* stream, InterpArgs<T> a, uint32_t ntarge
   while ((grid + band - 1) / band > 65535ull) band *= 2;
   hipLaunchKernelGGL((interp_columns<T, FUSED>), dim3((unsigned)band, ntarget, (unsigned)((grid + band - 1) / band)),
                      dim3(kThreads), lds, static_cast<hipStream_t>(stream), a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
-  return EKM_OK;
+  return launched(what);
 }
 
 // Height of pressure-level fields from their geopotential (vertical.py:330-345, 472-501, 1593-1601), the coordinate of
@@ -223,24 +219,19 @@ static int launch_height(int dev, void* stream, const T* z, const T* zs, size_t 
   if (mode < 2 || mode > 5) return set_error(EKM_ERR_ENUM, "height_from_geopotential: mode=%d", mode);
   if (!z || !out || ((mode == 4 || mode == 5) && !zs)) return set_error(EKM_ERR_ARG, "height_from_geopotential: null pointer");
   if (nlev > 65535u) return set_error(EKM_ERR_ARG, "height_from_geopotential: at most 65535 levels (got %u)", nlev);
-  for (const void* ptr : {(const void*)z, (const void*)zs, (const void*)out})
-    if (ptr && reinterpret_cast<uintptr_t>(ptr) % sizeof(T))
-      return set_error(EKM_ERR_ARG, "height_from_geopotential: a pointer is not aligned to its element size");
-  int rc = use_device(dev);
-  if (rc != EKM_OK) return rc;
+  int rc = check_aligned_if_given("height_from_geopotential", sizeof(T), {z, zs, out});
+  if (rc == EKM_OK) rc = use_device(dev);
   constexpr int V = VecOf<T>::N;
-  const unsigned long long nchunk = (npts + V - 1) / V;
-  const unsigned long long grid = (nchunk + kThreads - 1) / kThreads;
-  if (grid > 0x7fffffffull) return set_error(EKM_ERR_ARG, "height_from_geopotential: too many columns");
+  unsigned grid;
+  if (rc == EKM_OK) rc = launch_grid("height_from_geopotential", npts, kThreads * V, &grid);
+  if (rc != EKM_OK) return rc;
   unsigned long long band = (unsigned long long)tuning_hybrid_band_bytes() / ((unsigned long long)kThreads * V * sizeof(T));
   if (band < 8) band = 8;
   if (band > grid) band = grid;
   while ((grid + band - 1) / band > 65535ull) band *= 2;
   hipLaunchKernelGGL((height_rows<T>), dim3((unsigned)band, nlev, (unsigned)((grid + band - 1) / band)), dim3(kThreads), 0,
                      static_cast<hipStream_t>(stream), z, zs, (unsigned long long)npts, mode, out, (int)(npts % V == 0));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "height_from_geopotential launch: %s", hipGetErrorString(e));
-  return EKM_OK;
+  return launched("height_from_geopotential");
 }
 
 template <class T>

@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "../../include/ekm_thermo.h"
+#include "launch_checks.hpp"
 #include "map_kernel.hpp"
 #include "reduce_point.hpp"
 
@@ -90,27 +91,6 @@ __global__ __launch_bounds__(kRowWaves* kWaveLanes) void pearson_rows(const T* _
   if (lane == 0) out[row] = r;
 }
 
-static int red_pointers(const char* what, size_t elem, std::initializer_list<const void*> ptrs) {
-  for (const void* ptr : ptrs) {
-    if (!ptr) return set_error(EKM_ERR_ARG, "%s: null pointer", what);
-    if (reinterpret_cast<uintptr_t>(ptr) % elem)
-      return set_error(EKM_ERR_ARG, "%s: a pointer is not aligned to its element size (%d B)", what, (int)elem);
-  }
-  return EKM_OK;
-}
-
-static int red_grid(const char* what, unsigned long long blocks, unsigned* grid) {
-  if (blocks > 0x7fffffffull) return set_error(EKM_ERR_ARG, "%s: too many points", what);
-  *grid = (unsigned)blocks;
-  return EKM_OK;
-}
-
-static int red_launched(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
-  return EKM_OK;
-}
-
 template <class T, int NP>
 static void project_group(hipStream_t s, unsigned grid, const T* field, const T* coef, size_t k, size_t cstride, const T* scale,
                           size_t nfields, T* out) {
@@ -126,12 +106,11 @@ static int launch_project(int dev, void* stream, const T* field, size_t nfields,
   if (k > ~(size_t)0 / sizeof(T) / nfields) return set_error(EKM_ERR_ARG, "regimes_project: too many points");
   if (cstride != 0 && cstride < (size_t)npat * k)
     return set_error(EKM_ERR_ARG, "regimes_project: coef_stride=%zu is neither 0 nor at least npat * k = %zu", cstride, (size_t)npat * k);
-  int rc = red_pointers("regimes_project", sizeof(T), {field, coef, out});
+  int rc = check_pointers("regimes_project", sizeof(T), {field, coef, out});
   if (rc != EKM_OK) return rc;
-  if (scale && reinterpret_cast<uintptr_t>(scale) % sizeof(T))
-    return set_error(EKM_ERR_ARG, "regimes_project: scale is not aligned to its element size (%d B)", (int)sizeof(T));
+  if ((rc = check_aligned_if_given("regimes_project", sizeof(T), {scale})) != EKM_OK) return rc;
   unsigned grid;
-  if ((rc = red_grid("regimes_project", nfields, &grid)) != EKM_OK) return rc;
+  if ((rc = launch_grid("regimes_project", nfields, 1, &grid)) != EKM_OK) return rc;
   if ((rc = use_device(dev)) != EKM_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (uint32_t p0 = 0; p0 < npat; p0 += kProjGroup) {
@@ -147,7 +126,7 @@ static int launch_project(int dev, void* stream, const T* field, size_t nfields,
       case 7: project_group<T, 7>(s, grid, field, c, k, cstride, scale, nfields, o); break;
       default: project_group<T, 8>(s, grid, field, c, k, cstride, scale, nfields, o); break;
     }
-    if ((rc = red_launched("regimes_project")) != EKM_OK) return rc;
+    if ((rc = launched("regimes_project")) != EKM_OK) return rc;
   }
   return EKM_OK;
 }
@@ -156,16 +135,15 @@ template <class T>
 static int launch_index(int dev, void* stream, const T* proj, const T* mean, T mean_value, const T* std, T std_value, T* out,
                         size_t n) {
   if (n == 0) return EKM_OK;
-  int rc = red_pointers("regimes_index", sizeof(T), {proj, out});
+  int rc = check_pointers("regimes_index", sizeof(T), {proj, out});
   if (rc != EKM_OK) return rc;
-  if (reinterpret_cast<uintptr_t>(mean) % sizeof(T) || reinterpret_cast<uintptr_t>(std) % sizeof(T))
-    return set_error(EKM_ERR_ARG, "regimes_index: mean or std is not aligned to its element size (%d B)", (int)sizeof(T));
+  if ((rc = check_aligned_if_given("regimes_index", sizeof(T), {mean, std})) != EKM_OK) return rc;
   unsigned grid;
-  if ((rc = red_grid("regimes_index", ((unsigned long long)n + kPointLanes - 1) / kPointLanes, &grid)) != EKM_OK) return rc;
+  if ((rc = launch_grid("regimes_index", n, kPointLanes, &grid)) != EKM_OK) return rc;
   if ((rc = use_device(dev)) != EKM_OK) return rc;
   hipLaunchKernelGGL((standardise<T>), dim3(grid), dim3(kPointLanes), 0, static_cast<hipStream_t>(stream), proj, mean, mean_value,
                      std, std_value, (unsigned long long)n, out);
-  return red_launched("regimes_index");
+  return launched("regimes_index");
 }
 
 template <class T>
@@ -173,12 +151,12 @@ static int launch_pearson(int dev, void* stream, const T* x, const T* y, size_t 
   if (outer == 0 || inner == 0) return EKM_OK;
   if (m < 1) return set_error(EKM_ERR_ARG, "pearson: the sample axis is empty");
   if (inner > ~(size_t)0 / outer || m > ~(size_t)0 / sizeof(T) / (outer * inner)) return set_error(EKM_ERR_ARG, "pearson: too many points");
-  int rc = red_pointers("pearson", sizeof(T), {x, y, out});
+  int rc = check_pointers("pearson", sizeof(T), {x, y, out});
   if (rc != EKM_OK) return rc;
   const unsigned long long npts = (unsigned long long)outer * inner;
   unsigned grid;
   const int per_block = inner == 1 ? kRowWaves : kPointLanes;
-  if ((rc = red_grid("pearson", (npts + per_block - 1) / per_block, &grid)) != EKM_OK) return rc;
+  if ((rc = launch_grid("pearson", npts, per_block, &grid)) != EKM_OK) return rc;
   if ((rc = use_device(dev)) != EKM_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (inner == 1)
@@ -186,7 +164,7 @@ static int launch_pearson(int dev, void* stream, const T* x, const T* y, size_t 
   else
     hipLaunchKernelGGL((pearson_points<T>), dim3(grid), dim3(kPointLanes), 0, s, x, y, (unsigned long long)m,
                        (unsigned long long)inner, npts, out);
-  return red_launched("pearson");
+  return launched("pearson");
 }
 
 }  // namespace ekm

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "../../include/ekm_thermo.h"
+#include "launch_checks.hpp"
 #include "map_kernel.hpp"
 #include "solar_point.hpp"
 
@@ -23,73 +24,33 @@ namespace ekm {
 
 constexpr int kSolarThreads = 256;
 
-static_assert(EKM_SCALAR == 1 && EKM_LEVEL_MAJOR == 2 && EKM_LEVEL_MINOR == 3, "solar_point.hpp::solar_fetch and the header disagree");
-
 template <class T, class Out>
-__global__ __launch_bounds__(kSolarThreads) void solar_points(const SolarOperand<T> lat, const SolarOperand<T> lon,
+__global__ __launch_bounds__(kSolarThreads) void solar_points(const PointOperand<T> lat, const PointOperand<T> lon,
                                                               const double* __restrict__ nodes, unsigned nnodes,
                                                               unsigned long long n, int small, Out* __restrict__ out) {
   const unsigned long long p = (unsigned long long)blockIdx.x * kSolarThreads + threadIdx.x;
   if (p >= n) return;
-  const double la = solar_fetch<T>(lat, p, small != 0), lo = solar_fetch<T>(lon, p, small != 0);
+  const double la = point_fetch<T>(lat, p, small != 0), lo = point_fetch<T>(lon, p, small != 0);
   out[p] = solar_point<Out>(la, lo, nnodes, [&](unsigned k, int j) -> double { return nodes[(size_t)k * kSolarRecord + j]; });
-}
-
-template <class T>
-static int solar_operand(const char* name, const ekm_operand* op, size_t n, SolarOperand<T>* o, bool* small) {
-  if (!op || !op->data) return set_error(EKM_ERR_ARG, "solar: %s: null pointer", name);
-  if (reinterpret_cast<uintptr_t>(op->data) % sizeof(T))
-    return set_error(EKM_ERR_ARG, "solar: %s is not aligned to its element size (%d B)", name, (int)sizeof(T));
-  o->data = static_cast<const T*>(op->data);
-  o->mode = op->mode;
-  o->len = 1;
-  o->inner = 1;
-  switch (op->mode) {
-    case EKM_FIELD:
-    case EKM_SCALAR:
-      break;
-    case EKM_LEVEL_MAJOR:
-      if (op->len == 0 || op->inner == 0 || op->len < (n + op->inner - 1) / op->inner)
-        return set_error(EKM_ERR_ARG, "solar: %s: len * inner = %llu * %llu does not cover n = %llu", name,
-                         (unsigned long long)op->len, (unsigned long long)op->inner, (unsigned long long)n);
-      o->len = op->len;
-      o->inner = op->inner;
-      break;
-    case EKM_LEVEL_MINOR:
-      if (op->len == 0) return set_error(EKM_ERR_ARG, "solar: %s: an empty vector", name);
-      o->len = op->len;
-      break;
-    default:
-      return set_error(EKM_ERR_ARG, "solar: %s: mode %d is not EKM_FIELD, EKM_SCALAR, EKM_LEVEL_MAJOR or EKM_LEVEL_MINOR", name,
-                       op->mode);
-  }
-  if (o->len > 0xffffffffull || o->inner > 0xffffffffull) *small = false;
-  return EKM_OK;
 }
 
 template <class T, class Out>
 static int launch_solar(int dev, void* stream, const ekm_operand* lat, const ekm_operand* lon, const double* nodes,
                         uint32_t nnodes, Out* out, size_t n) {
   if (n == 0) return EKM_OK;
-  if (nnodes > 0 && (!nodes || reinterpret_cast<uintptr_t>(nodes) % sizeof(double)))
-    return set_error(EKM_ERR_ARG, "solar: the node records are null or not 8-B aligned");
-  if (!out || reinterpret_cast<uintptr_t>(out) % sizeof(Out))
-    return set_error(EKM_ERR_ARG, "solar: out is null or not aligned to its element size (%d B)", (int)sizeof(Out));
+  int rc = nnodes > 0 ? check_pointers("solar", sizeof(double), {nodes}) : EKM_OK;
+  if (rc == EKM_OK) rc = check_pointers("solar", sizeof(Out), {out});
+  if (rc != EKM_OK) return rc;
   bool small = (unsigned long long)n <= 0x100000000ull;  // 32-bit index arithmetic for the vector operands
-  SolarOperand<T> la, lo;
-  int rc = solar_operand<T>("latitudes", lat, n, &la, &small);
-  if (rc != EKM_OK) return rc;
-  rc = solar_operand<T>("longitudes", lon, n, &lo, &small);
-  if (rc != EKM_OK) return rc;
-  const unsigned long long g = ((unsigned long long)n + kSolarThreads - 1) / kSolarThreads;
-  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "solar: too many points");
-  rc = use_device(dev);
-  if (rc != EKM_OK) return rc;
-  hipLaunchKernelGGL((solar_points<T, Out>), dim3((unsigned)g), dim3(kSolarThreads), 0, static_cast<hipStream_t>(stream), la, lo,
+  PointOperand<T> la, lo;
+  if ((rc = check_point_operand<T>("solar", "latitudes", lat, n, &la, &small)) != EKM_OK) return rc;
+  if ((rc = check_point_operand<T>("solar", "longitudes", lon, n, &lo, &small)) != EKM_OK) return rc;
+  unsigned grid;
+  if ((rc = launch_grid("solar", n, kSolarThreads, &grid)) != EKM_OK) return rc;
+  if ((rc = use_device(dev)) != EKM_OK) return rc;
+  hipLaunchKernelGGL((solar_points<T, Out>), dim3(grid), dim3(kSolarThreads), 0, static_cast<hipStream_t>(stream), la, lo,
                      nodes, nnodes, (unsigned long long)n, small ? 1 : 0, out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "solar launch: %s", hipGetErrorString(e));
-  return EKM_OK;
+  return launched("solar");
 }
 
 }  // namespace ekm

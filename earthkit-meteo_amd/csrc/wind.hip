@@ -26,14 +26,13 @@
 #pragma clang fp contract(off)
 
 #include "../../include/ekm_thermo.h"
+#include "launch_checks.hpp"
 #include "map_kernel.hpp"
 #include "wind_point.hpp"
 
 namespace ekm {
 
 constexpr int kWindThreads = 256;
-
-static_assert(EKM_SCALAR == 1 && EKM_LEVEL_MAJOR == 2 && EKM_LEVEL_MINOR == 3, "solar_point.hpp::solar_fetch and the header disagree");
 
 template <int KIND, int WHICH>
 struct WindShape {
@@ -78,74 +77,35 @@ __global__ __launch_bounds__(kWindThreads) void wind_fields(const T* __restrict_
 
 // ---- some operand a scalar or a vector along one axis ----
 template <class T, int KIND, int MODE, int WHICH>
-__global__ __launch_bounds__(kWindThreads) void wind_bcast(const SolarOperand<T> a, const SolarOperand<T> b, T* __restrict__ out0,
+__global__ __launch_bounds__(kWindThreads) void wind_bcast(const PointOperand<T> a, const PointOperand<T> b, T* __restrict__ out0,
                                                            T* __restrict__ out1, unsigned long long n, int small) {
   typedef WindShape<KIND, WHICH> S;
   const unsigned long long p = (unsigned long long)blockIdx.x * kWindThreads + threadIdx.x;
   if (p >= n) return;
-  const T x = (T)solar_fetch<T>(a, p, small != 0);  // (solar_fetch hands the element back as a double: exact both ways)
-  const T y = S::NIN == 2 ? (T)solar_fetch<T>(b, p, small != 0) : T(0);
+  const T x = (T)point_fetch<T>(a, p, small != 0);  // (point_fetch hands the element back as a double: exact both ways)
+  const T y = S::NIN == 2 ? (T)point_fetch<T>(b, p, small != 0) : T(0);
   T o0, o1;
   wind_point<T, KIND, MODE, WHICH>(x, y, o0, o1);
   if constexpr (S::kOut0) out0[p] = o0;
   if constexpr (S::kOut1) out1[p] = o1;
 }
 
-template <class T>
-static int wind_operand(const char* what, const char* name, const ekm_operand* op, size_t n, SolarOperand<T>* o, bool* small,
-                        bool* fields) {
-  if (!op || !op->data) return set_error(EKM_ERR_ARG, "%s: %s: null pointer", what, name);
-  if (reinterpret_cast<uintptr_t>(op->data) % sizeof(T))
-    return set_error(EKM_ERR_ARG, "%s: %s is not aligned to its element size (%d B)", what, name, (int)sizeof(T));
-  o->data = static_cast<const T*>(op->data);
-  o->mode = op->mode;
-  o->len = 1;
-  o->inner = 1;
-  switch (op->mode) {
-    case EKM_FIELD:
-      break;
-    case EKM_SCALAR:
-      *fields = false;
-      break;
-    case EKM_LEVEL_MAJOR:
-      *fields = false;
-      if (op->len == 0 || op->inner == 0 || op->len < (n + op->inner - 1) / op->inner)
-        return set_error(EKM_ERR_ARG, "%s: %s: len * inner = %llu * %llu does not cover n = %llu", what, name,
-                         (unsigned long long)op->len, (unsigned long long)op->inner, (unsigned long long)n);
-      o->len = op->len;
-      o->inner = op->inner;
-      break;
-    case EKM_LEVEL_MINOR:
-      *fields = false;
-      if (op->len == 0) return set_error(EKM_ERR_ARG, "%s: %s: an empty vector", what, name);
-      o->len = op->len;
-      break;
-    default:
-      return set_error(EKM_ERR_ARG, "%s: %s: mode %d is not EKM_FIELD, EKM_SCALAR, EKM_LEVEL_MAJOR or EKM_LEVEL_MINOR", what, name,
-                       op->mode);
-  }
-  if (o->len > 0xffffffffull || o->inner > 0xffffffffull) *small = false;
-  return EKM_OK;
-}
-
 template <class T, int KIND, int MODE, int WHICH>
-static int launch_wind_as(int dev, hipStream_t s, const SolarOperand<T>& a, const SolarOperand<T>& b, bool fields, bool small, T* out0,
+static int launch_wind_as(int dev, hipStream_t s, const PointOperand<T>& a, const PointOperand<T>& b, bool fields, bool small, T* out0,
                           T* out1, size_t n) {
   constexpr int V = VecOf<T>::N;
   const unsigned long long items = fields ? ((unsigned long long)n / V > 0 ? (unsigned long long)n / V : 1ull) : (unsigned long long)n;
-  const unsigned long long g = (items + kWindThreads - 1) / kWindThreads;
-  if (g > 0x7fffffffull) return set_error(EKM_ERR_ARG, "wind: too many points");
-  int rc = use_device(dev);
+  unsigned g;
+  int rc = launch_grid("wind", items, kWindThreads, &g);
+  if (rc == EKM_OK) rc = use_device(dev);
   if (rc != EKM_OK) return rc;
   if (fields)
-    hipLaunchKernelGGL((wind_fields<T, KIND, MODE, WHICH>), dim3((unsigned)g), dim3(kWindThreads), 0, s, a.data, b.data, out0, out1,
+    hipLaunchKernelGGL((wind_fields<T, KIND, MODE, WHICH>), dim3(g), dim3(kWindThreads), 0, s, a.data, b.data, out0, out1,
                        (unsigned long long)n);
   else
-    hipLaunchKernelGGL((wind_bcast<T, KIND, MODE, WHICH>), dim3((unsigned)g), dim3(kWindThreads), 0, s, a, b, out0, out1,
+    hipLaunchKernelGGL((wind_bcast<T, KIND, MODE, WHICH>), dim3(g), dim3(kWindThreads), 0, s, a, b, out0, out1,
                        (unsigned long long)n, small ? 1 : 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "wind launch: %s", hipGetErrorString(e));
-  return EKM_OK;
+  return launched("wind");
 }
 
 template <class T, int KIND>
@@ -156,17 +116,14 @@ static int launch_wind(const char* what, int dev, void* stream, const ekm_operan
   if (mode < 0 || mode >= nmodes) return set_error(EKM_ERR_ENUM, "%s: convention %d out of range", what, mode);
   if (KIND == WIND_KIND_POLAR ? (!out0 && !out1) : (!out0 || (KIND == WIND_KIND_XY && !out1)))
     return set_error(EKM_ERR_ARG, "%s: an output is null", what);
-  if (reinterpret_cast<uintptr_t>(out0) % sizeof(T) || reinterpret_cast<uintptr_t>(out1) % sizeof(T))
-    return set_error(EKM_ERR_ARG, "%s: an output is not aligned to its element size (%d B)", what, (int)sizeof(T));
-  bool small = (unsigned long long)n <= 0x100000000ull, fields = true;
-  SolarOperand<T> oa, ob;
-  int rc = wind_operand<T>(what, "the first operand", a, n, &oa, &small, &fields);
+  int rc = check_aligned_if_given(what, sizeof(T), {out0, out1});
   if (rc != EKM_OK) return rc;
+  bool small = (unsigned long long)n <= 0x100000000ull, fields = true;
+  PointOperand<T> oa, ob;
+  if ((rc = check_point_operand<T>(what, "the first operand", a, n, &oa, &small, &fields)) != EKM_OK) return rc;
   ob = oa;
-  if (KIND != WIND_KIND_CORIOLIS) {
-    rc = wind_operand<T>(what, "the second operand", b, n, &ob, &small, &fields);
-    if (rc != EKM_OK) return rc;
-  }
+  if (KIND != WIND_KIND_CORIOLIS && (rc = check_point_operand<T>(what, "the second operand", b, n, &ob, &small, &fields)) != EKM_OK)
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
 #define EKM_WIND_GO(MODE_, WHICH_) return launch_wind_as<T, KIND, MODE_, WHICH_>(dev, s, oa, ob, fields, small, out0, out1, n)
   if constexpr (KIND == WIND_KIND_POLAR) {
@@ -261,15 +218,12 @@ static int launch_windrose(int dev, void* stream, const T* speed, const T* dir, 
   if (ns < 2 || nd < 3) return set_error(EKM_ERR_ARG, "windrose: needs at least 2 speed edges and 3 direction edges (got %u, %u)", ns, nd);
   if ((unsigned long long)ns + nd > kRoseMaxEdges)
     return set_error(EKM_ERR_ARG, "windrose: %u + %u edges, at most %u together", ns, nd, kRoseMaxEdges);
-  if (n > 0 && (!speed || !dir || reinterpret_cast<uintptr_t>(speed) % sizeof(T) || reinterpret_cast<uintptr_t>(dir) % sizeof(T)))
-    return set_error(EKM_ERR_ARG, "windrose: speed or direction is null or not aligned to its element size (%d B)", (int)sizeof(T));
-  if (!edges || !table || !out || reinterpret_cast<uintptr_t>(edges) % 8 || reinterpret_cast<uintptr_t>(table) % 8 ||
-      reinterpret_cast<uintptr_t>(out) % 8)
-    return set_error(EKM_ERR_ARG, "windrose: edges, table or out is null or not 8-B aligned");
+  int rc = n > 0 ? check_pointers("windrose", sizeof(T), {speed, dir}) : EKM_OK;
+  if (rc == EKM_OK) rc = check_pointers("windrose", 8, {edges, table, out});
+  if (rc != EKM_OK) return rc;
   if (!(inv_step == inv_step)) return set_error(EKM_ERR_ARG, "windrose: inv_step is NaN");
   const unsigned cells = (ns - 1) * (nd - 1);
-  int rc = use_device(dev);
-  if (rc != EKM_OK) return rc;
+  if ((rc = use_device(dev)) != EKM_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(table, 0, (size_t)cells * sizeof(unsigned long long), s);
   if (e != hipSuccess) return set_error(EKM_ERR_HIP, "windrose memset: %s", hipGetErrorString(e));
@@ -285,13 +239,10 @@ static int launch_windrose(int dev, void* stream, const T* speed, const T* dir, 
     else
       hipLaunchKernelGGL((windrose_count<T, false>), dim3((unsigned)g), dim3(kWindThreads), bytes, s, speed, dir, (unsigned long long)n, edges,
                          ns, nd, inv_step, cells, table);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(EKM_ERR_HIP, "windrose launch: %s", hipGetErrorString(e));
+    if ((rc = launched("windrose")) != EKM_OK) return rc;
   }
   hipLaunchKernelGGL(windrose_finish, dim3(1), dim3(kWindThreads), 0, s, table, ns - 1, nd - 1, percent, out);
-  e = hipGetLastError();
-  if (e != hipSuccess) return set_error(EKM_ERR_HIP, "windrose finish launch: %s", hipGetErrorString(e));
-  return EKM_OK;
+  return launched("windrose finish");
 }
 
 }  // namespace ekm

@@ -22,7 +22,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "solar_point.hpp"  // sol_sincos_deg, sol_fma, SolarOperand / solar_fetch
+#include "solar_point.hpp"  // sol_sincos_deg, sol_fma
 #include "thermo_math.hpp"
 
 namespace ekm {
