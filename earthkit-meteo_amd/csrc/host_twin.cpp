@@ -444,7 +444,77 @@ static int host_pearson(const T* x, const T* y, size_t outer, size_t m, size_t i
   }
   return 0;
 }
-#define EKM_HOST_REDUCE(tag, T)                                                                                              \
+// nanaverage: same arguments as ekm_nanaverage_* without dev / stream / work; `path` as there
+template <class T, bool W>
+static void host_nanavg_waves(const T* d, const T* w, size_t ws, size_t begin, size_t end, unsigned nthreads, T& s, ekm::nan_q_t<T, W>& q) {
+  // the lanes' partial pairs, a butterfly per wave, the waves in wave order
+  const unsigned nwaves = nthreads / ekm::kWaveLanes;
+  for (unsigned v = 0; v < nwaves; ++v) {
+    T ls[ekm::kWaveLanes];
+    ekm::nan_q_t<T, W> lq[ekm::kWaveLanes], wq;
+    for (unsigned l = 0; l < (unsigned)ekm::kWaveLanes; ++l)
+      ekm::nanavg_partial<T, W>(d, w, ws, begin, end, v * ekm::kWaveLanes + l, nthreads, ls[l], lq[l]);
+    const T wsum = ekm::host_wave_tree<T>(ls);
+    if constexpr (W) {
+      wq = ekm::host_wave_tree<T>(lq);
+    } else {
+      wq = 0;
+      for (unsigned l = 0; l < (unsigned)ekm::kWaveLanes; ++l) wq += lq[l];
+    }
+    if (v == 0)
+      s = wsum, q = wq;
+    else
+      ekm::nanavg_add<T, W>(s, q, wsum, wq);
+  }
+}
+template <class T, bool W>
+static int host_nanaverage_as(const T* data, size_t outer, size_t m, size_t inner, const T* w, size_t so, size_t sm, size_t si, int path,
+                              T* out) {
+  for (size_t p = 0; p < outer * inner; ++p) {
+    const size_t o = p / inner, j = p - o * inner;
+    if (path == ekm::kNanPoints) {
+      const size_t base = o * m * inner + j;
+      auto d = [&](size_t i) { return data[base + i * inner]; };
+      if constexpr (W) {
+        const T* wp = w + o * so + j * si;
+        out[p] = ekm::nanavg_point_weighted<T>(m, d, [&](size_t i) { return wp[i * sm]; });
+      } else {
+        out[p] = ekm::nanavg_point<T>(m, d);
+      }
+      continue;
+    }
+    const T* row = data + p * m;
+    const T* wrow = W ? w + p * so : nullptr;
+    T s;
+    ekm::nan_q_t<T, W> q;
+    if (path == ekm::kNanRows) {
+      host_nanavg_waves<T, W>(row, wrow, sm, 0, m, ekm::kWaveLanes, s, q);
+      out[p] = ekm::nanavg_finish<T, W>(s, q);
+      continue;
+    }
+    const size_t nchunks = ekm::nanavg_chunks(m);
+    T* pairs = new T[2 * nchunks];
+    for (size_t c = 0; c < nchunks; ++c) {
+      const size_t begin = c * ekm::kNanSplitChunk, end = begin + ekm::kNanSplitChunk < m ? begin + ekm::kNanSplitChunk : m;
+      host_nanavg_waves<T, W>(row, wrow, sm, begin, end, ekm::kNanSplitThreads, s, q);
+      pairs[2 * c] = s, pairs[2 * c + 1] = (T)q;
+    }
+    out[p] = ekm::nanavg_split_total<T, W>(pairs, nchunks);
+    delete[] pairs;
+  }
+  return 0;
+}
+template <class T>
+static int host_nanaverage(const T* data, size_t outer, size_t m, size_t inner, const T* w, size_t so, size_t sm, size_t si, int path,
+                           T* out) {
+  if (path < ekm::kNanAuto || path > ekm::kNanSplit) return -3;
+  if (outer == 0 || inner == 0) return 0;
+  if (path >= ekm::kNanRows && inner != 1) return -2;
+  if (path == ekm::kNanAuto) path = ekm::nanavg_path(outer, m, inner);
+  return w ? host_nanaverage_as<T, true>(data, outer, m, inner, w, so, sm, si, path, out)
+           : host_nanaverage_as<T, false>(data, outer, m, inner, nullptr, 0, 0, 0, path, out);
+}
+#define EKM_HOST_REDUCE(tag, T)                                                                                           \
   extern "C" int ekm_host_regimes_project_##tag(const T* field, size_t nfields, size_t k, const T* coef, unsigned npat,      \
                                                 size_t coef_stride, const T* scale, T* out) {                                \
     return host_project<T>(field, nfields, k, coef, npat, coef_stride, scale, out);                                          \
@@ -456,6 +526,10 @@ static int host_pearson(const T* x, const T* y, size_t outer, size_t m, size_t i
   }                                                                                                                          \
   extern "C" int ekm_host_pearson_##tag(const T* x, const T* y, size_t outer, size_t m, size_t inner, T* out) {              \
     return host_pearson<T>(x, y, outer, m, inner, out);                                                                      \
+  }                                                                                                                          \
+  extern "C" int ekm_host_nanaverage_##tag(const T* data, size_t outer, size_t m, size_t inner, const T* weights,            \
+                                           size_t wstride_outer, size_t wstride_m, size_t wstride_inner, int path, T* out) { \
+    return host_nanaverage<T>(data, outer, m, inner, weights, wstride_outer, wstride_m, wstride_inner, path, out);           \
   }
 EKM_HOST_REDUCE(f32, float)
 EKM_HOST_REDUCE(f64, double)

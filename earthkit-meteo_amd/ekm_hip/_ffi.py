@@ -103,6 +103,8 @@ def _signatures():
         sig[f"ekm_regimes_project_{tag}"] = ([i, vp, vp, sz, sz, vp, u32, sz, vp, vp], i)
         sig[f"ekm_regimes_index_{tag}"] = ([i, vp, vp, vp, real, vp, real, vp, sz], i)
         sig[f"ekm_pearson_{tag}"] = ([i, vp, vp, vp, sz, sz, sz, vp], i)
+        sig[f"ekm_nanaverage_{tag}"] = ([i, vp, vp, sz, sz, sz, vp, sz, sz, sz, i, vp, sz, vp], i)
+    sig["ekm_nanaverage_work_bytes"] = ([sz, sz, sz, sz, i, i], sz)
     sig["ekm_gumbel_cdf_f64"] = ([i, vp, vp, vp, sz, vp, u32, C.c_double, i, vp], i)
     sig["ekm_gumbel_ppf_f64"] = ([i, vp, vp, vp, sz, vp, u32, vp], i)
     for tag in ("f32", "f64", "f32_f64"):

@@ -48,16 +48,24 @@ Deviations of the Gumbel functions:
   * a `timedelta` freq works for NumPy distributions only (the host forms `freq / cdf` and `freq / return_period` as the
     reference does); for a device distribution it raises `TypeError`.
 The first use of a set of levels uploads it, which cannot be recorded: call once outside an `ekm_hip.graph()` block.
+
+`nanaverage(data, weights=None, **kwargs)` (reference stats/array/numpy_extended.py:13-61; kernels `nanavg_points`,
+`nanavg_rows`, `nanavg_split` in csrc/reduce.hip) is the NaN-skipping, optionally weighted mean along one axis, a run of
+adjacent axes or the whole array.  The data is read once (twice by the weighted mean along a non-contiguous axis) and
+nothing is stored but the result; weights that broadcast (a vector along the axis, `[lat, 1]`, a scalar) are read through
+strides, never expanded.  Nothing is uploaded but the operands, so a device-resident call can be recorded into a graph.
+Its docstring lists the deviations.
 """
 import datetime
 import math
 import numbers
+import operator
 
 import numpy as np
 
 from . import _ensemble as _e
 from ._ffi import GUMBEL_CDF, GUMBEL_RETURN_PERIOD, QUANTILE_LERP, QUANTILE_SORT
-from .device import DeviceArray, current_stream
+from .device import DeviceArray, _Allocation, current_stream
 from .vertical import _foreign_aware
 
 _F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)
@@ -133,6 +141,126 @@ def quantiles(arr, which=100, axis=0, method="sort"):
         device, stream, d_arr.ptr, outer, m, inner, tabs[0].on(stream), tabs[1].on(stream), tabs[2].on(stream), nq,
         QUANTILE_SORT if method == "sort" else QUANTILE_LERP, out.on(stream)))
     return _e.finish(out, _e.on_device(arr))
+
+
+def _nanaverage_run(axis, ndim, weighted):
+    """(first, last) of the run of adjacent dimensions that `axis` names, or None for all of them."""
+    if axis is None:
+        return None
+    if isinstance(axis, tuple):
+        if weighted:  # the reference fails on `reshape[axis] = 1` with a list-index TypeError
+            raise TypeError(f"nanaverage: with weights, axis must be None or an int, not the tuple {axis}")
+        named = []
+        for a in axis:
+            a = operator.index(a)
+            if not -ndim <= a < ndim:
+                raise np.exceptions.AxisError(a, ndim)
+            named.append(a % ndim)
+        run = sorted(named)
+        if not run or len(set(run)) != len(run) or run != list(range(run[0], run[-1] + 1)):
+            raise ValueError(f"nanaverage: axis={axis} must name distinct adjacent dimensions (one run, such as (-2, -1)); "
+                             f"of {ndim} dimensions it names {tuple(named)}")
+        return run[0], run[-1]
+    a = operator.index(axis)
+    if not -ndim <= a < ndim:
+        raise np.exceptions.AxisError(a, ndim)
+    return a % ndim, a % ndim
+
+
+def _nanaverage_weight_strides(wshape, shape, first, last):
+    """The element strides (outer, m, inner) under which C-contiguous weights of `wshape`, broadcast against `shape`, are
+    read on the [outer, m, inner] view (0 = broadcast), or None when a group of dimensions does not collapse to one."""
+    nd = len(shape)
+    w = (1,) * (nd - len(wshape)) + tuple(wshape)
+    strides, acc = [0] * nd, 1
+    for k in reversed(range(nd)):
+        strides[k] = 0 if w[k] == 1 else acc
+        acc *= w[k]
+    out = []
+    for lo, hi in ((0, first), (first, last + 1), (last + 1, nd)):
+        stride = expect = None
+        for k in reversed(range(lo, hi)):
+            if shape[k] == 1:
+                continue
+            if stride is None:
+                stride = strides[k]
+            elif strides[k] != expect:
+                return None
+            expect = strides[k] * shape[k]
+        out.append(stride or 0)
+    return tuple(out)
+
+
+@_foreign_aware("data", "weights")
+def nanaverage(data, weights=None, **kwargs):
+    """A merge of the functionality of np.nanmean and np.average (numpy_extended.py:13-61): the mean of `data` along
+    `axis` where NaN values are ignored and `weights` are applied if given.
+
+    weights: anything NumPy broadcasts against data's shape; normalised by the sum of the valid weights of every slice.  A
+    sample whose weight is NaN is skipped like one whose datum is NaN.
+    kwargs: axis (None: the whole array; an int; for the unweighted mean also a tuple of adjacent axes) and keepdims.
+
+    The result is float32 only when every array given is float32, float64 otherwise.  Along an axis that is not the
+    contiguous one the result is the reference's bit for bit; along the contiguous axis (and for axis=None) NumPy adds
+    pairwise and the kernels lane by lane, so the result is within a rounding bound of the exact mean
+    (tests/_nanaverage_numpy.py).  An all-NaN slice gives NaN without weights and 0.0 with them, as in the reference.
+
+    Deviations: a tuple of axes must name one run of adjacent dimensions (ValueError otherwise); the other keywords of
+    numpy.nansum / numpy.nanmean (dtype, out, where, initial) raise TypeError; weights that would enlarge data's shape
+    raise ValueError (the reference fails later, with a boolean-index error); no RuntimeWarning is issued for an empty
+    slice; float16 input is computed and returned as float64; integer data with integer weights is computed in float64 (the
+    reference fails there, writing NaN into an integer array)."""
+    for key in kwargs:
+        if key not in ("axis", "keepdims"):
+            raise TypeError(f"nanaverage: the keyword {key!r} is not supported (axis and keepdims are)")
+    axis, keepdims = kwargs.get("axis"), bool(kwargs.get("keepdims", False))
+    data = _e.as_input(data)
+    weighted = weights is not None
+    if weighted:
+        weights = _e.as_input(weights)
+    shape = tuple(int(v) for v in data.shape)
+    nd = len(shape)
+    run = _nanaverage_run(axis, nd, weighted)
+    first, last = (0, nd - 1) if run is None else run
+    outer, m, inner = math.prod(shape[:first]), math.prod(shape[first:last + 1]), math.prod(shape[last + 1:])
+    rest = shape[:first] + ((1,) * (last - first + 1) if keepdims else ()) + shape[last + 1:]
+    wstrides = (0, 0, 0)
+    if weighted:
+        wshape = tuple(int(v) for v in weights.shape)
+        try:
+            fits = np.broadcast_shapes(wshape, shape) == shape
+        except ValueError:
+            fits = False
+        if not fits:
+            raise ValueError(f"nanaverage: weights of shape {wshape} do not broadcast against the data's shape {shape}")
+        wstrides = _nanaverage_weight_strides(wshape, shape, first, last)
+    dtype = _e.arith_dtype(data, weights) if weighted else _e.arith_dtype(data)
+    device_result = _e.on_device(data, weights) if weighted else _e.on_device(data)
+    if outer * inner == 0 and not device_result:
+        return np.empty(rest, dtype)  # no work: no device is asked for
+    device, stream, keep = (_e.device_of(data, weights) if weighted else _e.device_of(data)), current_stream(), []
+    out = DeviceArray.empty(rest, dtype, device)
+    if outer * inner == 0:
+        return out
+    d_data = _e.upload(data, dtype, device, stream, keep)
+    d_w = None
+    if weighted:
+        if wstrides is None:  # the broadcast does not collapse onto [outer, m, inner]: expanded once, on the host
+            host = weights.to_host() if isinstance(weights, DeviceArray) else weights
+            weights, wstrides = np.ascontiguousarray(np.broadcast_to(host, shape)), (m * inner, inner, 1)
+        d_w = _e.upload(weights, dtype, device, stream, keep)
+    lib = _e.lib()
+    need = int(lib.ekm_nanaverage_work_bytes(dtype.itemsize, outer, m, inner, int(weighted), 0))
+    work = None
+    if need:  # the split path's partial sums: the block belongs to this call (and to the graph that records it)
+        work = _Allocation(need, device)
+        work.touch(stream)
+    _e._ffi.check(getattr(lib, "ekm_nanaverage_" + _e.tag_of(dtype))(
+        device, stream, d_data.ptr, outer, m, inner, d_w.ptr if weighted else None, *wstrides, 0,
+        work.ptr if work is not None else None, need, out.on(stream)))
+    if work is not None:
+        work.free()  # back to the block cache of this stream: a later user is ordered after the kernels
+    return out if device_result else _e.finish(out, False)[()]
 
 
 def iter_quantiles(arr, which=100, axis=0, method="sort"):

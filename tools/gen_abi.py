@@ -177,7 +177,7 @@ typedef struct ekm_operand {
  *      Crossing Point Forecast ekm_cpf_*; the solar geometry ekm_solar_*; the wind functions
  *      ekm_wind_polar_*, ekm_wind_xy_*, ekm_wind_coriolis_*, ekm_windrose_*; the Gumbel extreme-value fit and its
  *      functions ekm_gumbel_fit_*, ekm_gumbel_cdf_f64, ekm_gumbel_ppf_f64; the reduce family ekm_regimes_project_*,
- *      ekm_regimes_index_*, ekm_pearson_*. */
+ *      ekm_regimes_index_*, ekm_pearson_*; the NaN-skipping weighted mean ekm_nanaverage_*, ekm_nanaverage_work_bytes. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -505,6 +505,31 @@ EKM_API int ekm_pearson_f32(int dev, void* stream, const float* x, const float* 
                             float* out);
 EKM_API int ekm_pearson_f64(int dev, void* stream, const double* x, const double* y, size_t outer, size_t m, size_t inner,
                             double* out);
+/* ekm_nanaverage_*: reference stats/array/numpy_extended.py:13-61 (nanaverage).
+ *   data: [outer, m, inner] contiguous, out: [outer * inner]: the mean along m of the samples that are not NaN.
+ *   weights: NULL for the plain mean (numpy.nanmean), else the weight of data[o, i, j] is
+ *   weights[o * wstride_outer + i * wstride_m + j * wstride_inner] (strides in elements, 0 = broadcast); a sample whose
+ *   datum or weight is NaN is skipped.  No valid sample: NaN unweighted, 0 weighted (as the reference); m may be 0.
+ *   path: 0 = chosen from (outer, m, inner) alone; 1 = points (one lane per output point, samples added in order: NumPy's
+ *   order along a non-contiguous axis, the result is the reference's bit for bit; any inner); 2 = rows (one wave per row);
+ *   3 = split (one workgroup per chunk of 32768 elements of a row, the chunks' partial pairs added in chunk order by a
+ *   second kernel).  2 and 3 need inner == 1 (else EKM_ERR_ARG); another value is EKM_ERR_ENUM.  path 0 takes 1 when
+ *   inner > 1, else 3 when m >= 65536 and outer < 2048, else 2.
+ *   work: device scratch of the split path, ekm_nanaverage_work_bytes(...) bytes, aligned to the element; may hold
+ *   anything on entry and belongs to the call until it has run; NULL / 0 on the other paths.  Too small is EKM_ERR_ARG.
+ *   The unweighted sums start at +0 and are divided by the count in double, rounded once.  Weighted: path 1 forms
+ *   den = sum w, then sum data * (w / den), as the reference does; paths 2 and 3 form sum data * w and sum w in one pass
+ *   and divide once.  No atomics: the same call gives the same bytes, a row the same bits at any row index and address.
+ *   Only enqueues kernels: nothing allocates, copies or waits on the host.
+ * ekm_nanaverage_work_bytes: reference stats/array/numpy_extended.py:13-61; host only, needs no device: the bytes of
+ *   `work` that ekm_nanaverage_* with these arguments needs (0 where it needs none, and for arguments it refuses). */
+EKM_API int ekm_nanaverage_f32(int dev, void* stream, const float* data, size_t outer, size_t m, size_t inner,
+                               const float* weights, size_t wstride_outer, size_t wstride_m, size_t wstride_inner, int path,
+                               void* work, size_t work_bytes, float* out);
+EKM_API int ekm_nanaverage_f64(int dev, void* stream, const double* data, size_t outer, size_t m, size_t inner,
+                               const double* weights, size_t wstride_outer, size_t wstride_m, size_t wstride_inner, int path,
+                               void* work, size_t work_bytes, double* out);
+EKM_API size_t ekm_nanaverage_work_bytes(size_t elem_size, size_t outer, size_t m, size_t inner, int weighted, int path);
 
 /* ---- solar geometry: cosine of the solar zenith angle, its time average, top-of-atmosphere incident radiation ----
  * Reference solar/array/solar.py:51-96 (cos_solar_zenith_angle), :99-179 (_integrate), :182-254.  One launch, one lane per
