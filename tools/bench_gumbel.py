@@ -3,8 +3,8 @@
 
 Field: 721 x 1440 points (a 0.25-degree global grid).  `fit` runs on 51 and on 86 annual maxima per point (Gumbel
 distributed, from 65 536 distinct columns tiled over the field), sample axis first, f32 and f64; `cdf` on the fitted
-parameters at 1 and at 8 levels, as the cdf and as the return period.  Every GPU timing is HIP events around `--steps`
-launches after `--warmup`, in ONE process on the same arrays.  Beside each time:
+parameters at 1 and at 8 levels, as the cdf and as the return period.  How the GPU timings are taken: tools/_benchlib.py.
+Beside each time:
   copy_ms_same_bytes   the time ekm_stream_mix (one stream in, one out, no arithmetic) needs for the same number of bytes
                        at the rate it reaches on this run's arrays;
   numpy_ms             the reference's arithmetic with NumPy on the host, once: sort and the two running sums for `fit`
@@ -13,19 +13,12 @@ Byte model: fit reads m * itemsize and writes 16 B per point; cdf reads 16 B and
 
 Usage: python tools/bench_gumbel.py [--steps 10 --warmup 3 --out profiles/gumbel_bench.json]
 """
-import argparse
-import ctypes as C
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "earthkit-meteo_amd"))
+import _benchlib as bl
 
-HBM_PEAK = 8.0e12
 NPTS, DISTINCT = 721 * 1440, 1 << 16
 LN2 = 0.6931471805599453
 
@@ -43,88 +36,59 @@ def numpy_fit(sample):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gumbel_bench.json"))
-    args = ap.parse_args()
+    args = bl.parser("gumbel_bench.json").parse_args()
 
     import ekm_hip
     from ekm_hip import _ffi
 
-    lib, dev = _ffi.lib(), 0
-    _ffi.check(lib.ekm_init())
-    name = C.create_string_buffer(128)
-    lib.ekm_device_name(dev, name, 128)
-    result = dict(npts=NPTS, steps=args.steps, warmup=args.warmup, device=name.value.decode(), hbm_peak_bytes_per_s=HBM_PEAK, runs=[])
-    ev = [C.c_void_p(), C.c_void_p()]
-    for e in ev:
-        _ffi.check(lib.ekm_event_create(dev, C.byref(e)))
+    lib, dev, name = bl.open_device()
+    result = dict(npts=NPTS, steps=args.steps, warmup=args.warmup, device=name, hbm_peak_bytes_per_s=bl.HBM_PEAK, runs=[])
 
-    def timed(launch):
-        for _ in range(args.warmup):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[0], None))
-        for _ in range(args.steps):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[1], None))
-        _ffi.check(lib.ekm_event_sync(dev, ev[1]))
-        ms = C.c_float()
-        _ffi.check(lib.ekm_event_elapsed_ms(dev, ev[0], ev[1], C.byref(ms)))
-        return ms.value / args.steps
+    with bl.EventTimer(lib, dev, args.steps, args.warmup) as timer:
+        def copy_rate(src, dst, nbytes):
+            return 2 * nbytes / (timer.copy([src.ptr], [dst.ptr], nbytes) * 1e-3)
 
-    def copy_rate(src, dst, nbytes):
-        ins, outs = (C.c_void_p * 1)(src.ptr), (C.c_void_p * 1)(dst.ptr)
-        ms = timed(lambda: _ffi.check(lib.ekm_stream_mix(dev, None, ins, 1, outs, 1, nbytes)))
-        return 2 * nbytes / (ms * 1e-3)
+        def report(run, ms, nbytes, rate):
+            bl.emit(result, "runs", dict(run, kernel_ms=ms, algorithmic_bytes=nbytes, **bl.derived(ms, nbytes, rate, NPTS)))
 
-    def report(run, ms, nbytes, rate):
-        run.update(kernel_ms=ms, algorithmic_bytes=nbytes, bytes_per_s=nbytes / (ms * 1e-3), copy_bytes_per_s=rate,
-                   copy_ms_same_bytes=nbytes / rate * 1e3, frac_copy_rate=nbytes / (ms * 1e-3) / rate,
-                   frac_hbm_peak=nbytes / (ms * 1e-3) / HBM_PEAK, points_per_s=NPTS / (ms * 1e-3))
-        result["runs"].append(run)
-        print(json.dumps(run), flush=True)
-
-    rng = np.random.default_rng(1)
-    mu = ekm_hip.DeviceArray.empty((NPTS,), np.float64)
-    sigma = ekm_hip.DeviceArray.empty((NPTS,), np.float64)
-    for m in (51, 86):
-        base = rng.gumbel(20.0, 5.0, (m, DISTINCT))
-        pick = np.arange(NPTS) % DISTINCT
-        for dtype in (np.float32, np.float64):
-            dt = np.dtype(dtype)
-            tag = "f32" if dt == np.float32 else "f64"
-            host = np.ascontiguousarray(base[:, pick].astype(dt))
-            sample = ekm_hip.DeviceArray.from_host(host)
-            scratch = ekm_hip.DeviceArray.empty((m, NPTS), dt)
-            rate = copy_rate(sample, scratch, sample.nbytes)
-            fn = getattr(lib, "ekm_gumbel_fit_" + tag)
-            ms = timed(lambda: _ffi.check(fn(dev, None, sample.ptr, 1, m, NPTS, mu.ptr, sigma.ptr)))
+        rng = np.random.default_rng(1)
+        mu = ekm_hip.DeviceArray.empty((NPTS,), np.float64)
+        sigma = ekm_hip.DeviceArray.empty((NPTS,), np.float64)
+        for m in (51, 86):
+            base = rng.gumbel(20.0, 5.0, (m, DISTINCT))
+            pick = np.arange(NPTS) % DISTINCT
+            for dtype in (np.float32, np.float64):
+                dt = np.dtype(dtype)
+                tag = bl.tag(dt)
+                host = np.ascontiguousarray(base[:, pick].astype(dt))
+                sample = ekm_hip.DeviceArray.from_host(host)
+                scratch = ekm_hip.DeviceArray.empty((m, NPTS), dt)
+                rate = copy_rate(sample, scratch, sample.nbytes)
+                fn = getattr(lib, "ekm_gumbel_fit_" + tag)
+                ms = timer.mean(lambda: _ffi.check(fn(dev, None, sample.ptr, 1, m, NPTS, mu.ptr, sigma.ptr)))
+                t0 = time.perf_counter()
+                numpy_fit(host)
+                numpy_ms = (time.perf_counter() - t0) * 1e3
+                report(dict(case=f"fit_m{m}", dtype=tag, numpy_ms=numpy_ms), ms, (m * dt.itemsize + 16) * NPTS, rate)
+                _ffi.check(lib.ekm_sync(dev))
+                sample.free(), scratch.free()
+        # cdf on the parameters the last fit left (86 samples, f64)
+        h_mu, h_sigma = mu.to_host(), sigma.to_host()
+        out = ekm_hip.DeviceArray.empty((8, NPTS), np.float64)
+        scratch = ekm_hip.DeviceArray.empty((8, NPTS), np.float64)
+        rate = copy_rate(out, scratch, out.nbytes)
+        for nx in (1, 8):
+            levels = np.linspace(25.0, 60.0, nx)
+            d_levels = ekm_hip.DeviceArray.from_host(levels)
             t0 = time.perf_counter()
-            numpy_fit(host)
+            with np.errstate(all="ignore"):
+                1.0 - np.exp(-np.exp((h_mu - levels[:, None]) / h_sigma))
             numpy_ms = (time.perf_counter() - t0) * 1e3
-            report(dict(case=f"fit_m{m}", dtype=tag, numpy_ms=numpy_ms), ms, (m * dt.itemsize + 16) * NPTS, rate)
+            for what, mode in (("cdf", 0), ("return_period", 1)):
+                ms = timer.mean(lambda: _ffi.check(lib.ekm_gumbel_cdf_f64(dev, None, mu.ptr, sigma.ptr, NPTS, d_levels.ptr, nx, 1.0, mode, out.ptr)))
+                report(dict(case=f"{what}_nx{nx}", dtype="f64", numpy_ms=numpy_ms), ms, (16 + 8 * nx) * NPTS, rate)
             _ffi.check(lib.ekm_sync(dev))
-            sample.free(), scratch.free()
-    # cdf on the parameters the last fit left (86 samples, f64)
-    h_mu, h_sigma = mu.to_host(), sigma.to_host()
-    out = ekm_hip.DeviceArray.empty((8, NPTS), np.float64)
-    scratch = ekm_hip.DeviceArray.empty((8, NPTS), np.float64)
-    rate = copy_rate(out, scratch, out.nbytes)
-    for nx in (1, 8):
-        levels = np.linspace(25.0, 60.0, nx)
-        d_levels = ekm_hip.DeviceArray.from_host(levels)
-        t0 = time.perf_counter()
-        with np.errstate(all="ignore"):
-            1.0 - np.exp(-np.exp((h_mu - levels[:, None]) / h_sigma))
-        numpy_ms = (time.perf_counter() - t0) * 1e3
-        for what, mode in (("cdf", 0), ("return_period", 1)):
-            ms = timed(lambda: _ffi.check(lib.ekm_gumbel_cdf_f64(dev, None, mu.ptr, sigma.ptr, NPTS, d_levels.ptr, nx, 1.0, mode, out.ptr)))
-            report(dict(case=f"{what}_nx{nx}", dtype="f64", numpy_ms=numpy_ms), ms, (16 + 8 * nx) * NPTS, rate)
-        _ffi.check(lib.ekm_sync(dev))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f, indent=1, sort_keys=True)
+    bl.write(args.out, result)
 
 
 if __name__ == "__main__":

@@ -2,8 +2,7 @@
 """Times the vertical interpolation kernels on one GPU and writes profiles/interp_bench.json.
 
 Field: 3600 x 1800 columns x 137 levels (the benchmark field of bench.py), surface pressure 520-1040 hPa, pressure
-targets: the 10 mandatory and the 37 standard pressure levels.  Every timing is HIP events around `--steps` launches
-after `--warmup`, in ONE process on the same arrays:
+targets: the 10 mandatory and the 37 standard pressure levels.  How the timings are taken: tools/_benchlib.py.
   fused       ekm_interpolate_hybrid_to_pressure_*: p formed in the kernel;
   two_step    ekm_pressure_on_hybrid_levels_* writing p, then ekm_interpolate_monotonic_* reading it (the sanity
               relation: the fused kernel should beat it);
@@ -18,7 +17,6 @@ of N columns split over `--workers` processes, for the speed-up's denominator; n
 
 Usage: python tools/bench_interp.py [--steps 10 --warmup 3 --nx 3600 --ny 1800 --out profiles/interp_bench.json]
 """
-import argparse
 import ctypes as C
 import json
 import os
@@ -27,10 +25,8 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "earthkit-meteo_amd"))
+import _benchlib as bl
 
-HBM_PEAK = 8.0e12
 P10 = [1000, 925, 850, 700, 500, 400, 300, 250, 200, 100]
 P37 = [1000, 975, 950, 925, 900, 875, 850, 825, 800, 775, 750, 700, 650, 600, 550, 500, 450, 400, 350, 300, 250, 225, 200,
        175, 150, 125, 100, 70, 50, 30, 20, 10, 7, 5, 3, 2, 1]
@@ -55,7 +51,7 @@ def _ref_slab(args):
 def reference_time(path, ncol, workers):
     import multiprocessing as mp
 
-    standin = os.path.join(ROOT, "tests", "golden", "_standin")
+    standin = os.path.join(bl.ROOT, "tests", "golden", "_standin")
     per = ncol // workers
     t0 = time.perf_counter()
     with mp.get_context("spawn").Pool(workers) as pool:
@@ -68,18 +64,15 @@ def reference_time(path, ncol, workers):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = bl.parser("interp_bench.json")
     ap.add_argument("--nx", type=int, default=3600)
     ap.add_argument("--ny", type=int, default=1800)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "interp_bench.json"))
     ap.add_argument("--reference", default=None)
     ap.add_argument("--slab-columns", type=int, default=16 * 40500)
     ap.add_argument("--workers", type=int, default=16)
     args = ap.parse_args()
 
-    result = dict(field=[137, args.ny, args.nx], steps=args.steps, warmup=args.warmup, hbm_peak_bytes_per_s=HBM_PEAK, runs=[])
+    result = dict(field=[137, args.ny, args.nx], steps=args.steps, warmup=args.warmup, hbm_peak_bytes_per_s=bl.HBM_PEAK, runs=[])
     if args.reference:
         result["reference_numpy"] = reference_time(args.reference, args.slab_columns, args.workers)
         if os.path.exists(args.out):  # keep the GPU numbers of an earlier run
@@ -87,8 +80,7 @@ def main():
                 old = json.load(f)
             old["reference_numpy"] = result["reference_numpy"]
             result = old
-        with open(args.out, "w") as f:
-            json.dump(result, f, indent=1, sort_keys=True)
+        bl.write(args.out, result)
         print(json.dumps(result["reference_numpy"]))
         return
 
@@ -96,75 +88,52 @@ def main():
     from ekm_hip import _ffi
     from ekm_hip.vertical import hybrid_level_parameters
 
-    lib, dev = _ffi.lib(), 0
-    _ffi.check(lib.ekm_init())
-    name = C.create_string_buffer(128)
-    lib.ekm_device_name(dev, name, 128)
-    result["device"] = name.value.decode()
+    lib, dev, result["device"] = bl.open_device()
     npts, nlev = args.nx * args.ny, 137
     A64, B64 = hybrid_level_parameters(137)
     rng = np.random.default_rng(1)
-    ev = [C.c_void_p(), C.c_void_p()]
-    for e in ev:
-        _ffi.check(lib.ekm_event_create(dev, C.byref(e)))
 
-    def timed(launch):
-        for _ in range(args.warmup):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[0], None))
-        for _ in range(args.steps):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[1], None))
-        _ffi.check(lib.ekm_event_sync(dev, ev[1]))
-        ms = C.c_float()
-        _ffi.check(lib.ekm_event_elapsed_ms(dev, ev[0], ev[1], C.byref(ms)))
-        return ms.value / args.steps
+    def part(nbytes, ms, copy_rate, **more):
+        d = bl.derived(ms, nbytes, copy_rate)
+        return dict(algorithmic_bytes=nbytes, bytes_per_s=d["bytes_per_s"], frac_hbm_peak=d["frac_hbm_peak"],
+                    frac_copy_rate=d["frac_copy_rate"], **more)
 
-    for dtype, targets in ((np.float32, (P10, P37)), (np.float64, (P37,))):
-        dt = np.dtype(dtype)
-        tag, real = ("f32", C.c_float) if dt == np.float32 else ("f64", C.c_double)
-        d_a, d_b = (ekm_hip.DeviceArray.from_host(x.astype(dt)) for x in (A64, B64))
-        d_sp = ekm_hip.DeviceArray.from_host(rng.uniform(52000.0, 104000.0, npts).astype(dt))
-        data = ekm_hip.DeviceArray.empty((nlev, npts), dt)
-        level = rng.uniform(200.0, 300.0, npts).astype(dt)
-        for k in range(nlev):  # one random level, shifted per level: the values do not matter to the timing, the bracket does
-            data.flat_slice(k * npts, (k + 1) * npts).copy_from_host(level + dt.type(k))
-        p = ekm_hip.DeviceArray.empty((nlev, npts), dt)
-        for tp in targets:
-            nt = len(tp)
-            d_t = ekm_hip.DeviceArray.from_host(100.0 * np.asarray(tp, dtype=dt))
-            out = ekm_hip.DeviceArray.empty((nt, npts), dt)
-            null = None
-            fused = lambda: _ffi.check(getattr(lib, f"ekm_interpolate_hybrid_to_pressure_{tag}")(  # noqa: E731
-                dev, None, data.ptr, d_a.ptr, d_b.ptr, d_sp.ptr, d_t.ptr, 0, nt, npts, nlev, 0, 0, null, null, null, null, 0, out.ptr))
-            pressure = lambda: _ffi.check(getattr(lib, f"ekm_pressure_on_hybrid_levels_{tag}")(  # noqa: E731
-                dev, None, d_a.ptr, d_b.ptr, d_sp.ptr, npts, nlev, None, None, 1, real(float(np.log(2))), p.ptr, None, None, None))
-            generic = lambda: _ffi.check(getattr(lib, f"ekm_interpolate_monotonic_{tag}")(  # noqa: E731
-                dev, None, data.ptr, p.ptr, 1, d_t.ptr, 0, nt, npts, nlev, 0, 0, null, null, null, null, 0, out.ptr))
-            ins, outs = (C.c_void_p * 1)(data.ptr), (C.c_void_p * 1)(out.ptr)
-            copy = lambda: _ffi.check(lib.ekm_stream_mix(dev, None, ins, 1, outs, 1, out.nbytes))  # noqa: E731
-            pressure()
-            ms = dict(fused=timed(fused), generic=timed(generic), two_step=timed(lambda: (pressure(), generic())), copy=timed(copy))
-            copy_rate = 2 * out.nbytes / (ms["copy"] * 1e-3)
-            fused_bytes = dt.itemsize * (3 * nt * npts + npts)
-            generic_bytes = dt.itemsize * 5 * nt * npts
-            run = dict(dtype=tag, ntarget=nt, kernel_ms=ms, copy_bytes_per_s=copy_rate,
-                       fused=dict(algorithmic_bytes=fused_bytes, bytes_per_s=fused_bytes / (ms["fused"] * 1e-3),
-                                  frac_hbm_peak=fused_bytes / (ms["fused"] * 1e-3) / HBM_PEAK,
-                                  frac_copy_rate=fused_bytes / (ms["fused"] * 1e-3) / copy_rate,
-                                  output_points_per_s=nt * npts / (ms["fused"] * 1e-3)),
-                       generic=dict(algorithmic_bytes=generic_bytes, bytes_per_s=generic_bytes / (ms["generic"] * 1e-3),
-                                    frac_hbm_peak=generic_bytes / (ms["generic"] * 1e-3) / HBM_PEAK,
-                                    frac_copy_rate=generic_bytes / (ms["generic"] * 1e-3) / copy_rate),
-                       fused_over_two_step=ms["fused"] / ms["two_step"])
-            result["runs"].append(run)
-            print(json.dumps(run), flush=True)
-            out.free(), d_t.free()
-        for x in (data, p, d_sp, d_a, d_b):
-            x.free()
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f, indent=1, sort_keys=True)
+    with bl.EventTimer(lib, dev, args.steps, args.warmup) as timer:
+        for dtype, targets in ((np.float32, (P10, P37)), (np.float64, (P37,))):
+            dt = np.dtype(dtype)
+            tag, real = bl.tag(dt), C.c_float if dt == np.float32 else C.c_double
+            d_a, d_b = (ekm_hip.DeviceArray.from_host(x.astype(dt)) for x in (A64, B64))
+            d_sp = ekm_hip.DeviceArray.from_host(rng.uniform(52000.0, 104000.0, npts).astype(dt))
+            data = ekm_hip.DeviceArray.empty((nlev, npts), dt)
+            level = rng.uniform(200.0, 300.0, npts).astype(dt)
+            for k in range(nlev):  # one random level, shifted per level: the values do not matter to the timing, the bracket does
+                data.flat_slice(k * npts, (k + 1) * npts).copy_from_host(level + dt.type(k))
+            p = ekm_hip.DeviceArray.empty((nlev, npts), dt)
+            for tp in targets:
+                nt = len(tp)
+                d_t = ekm_hip.DeviceArray.from_host(100.0 * np.asarray(tp, dtype=dt))
+                out = ekm_hip.DeviceArray.empty((nt, npts), dt)
+                null = None
+                fused = lambda: _ffi.check(getattr(lib, f"ekm_interpolate_hybrid_to_pressure_{tag}")(  # noqa: E731
+                    dev, None, data.ptr, d_a.ptr, d_b.ptr, d_sp.ptr, d_t.ptr, 0, nt, npts, nlev, 0, 0, null, null, null, null, 0, out.ptr))
+                pressure = lambda: _ffi.check(getattr(lib, f"ekm_pressure_on_hybrid_levels_{tag}")(  # noqa: E731
+                    dev, None, d_a.ptr, d_b.ptr, d_sp.ptr, npts, nlev, None, None, 1, real(float(np.log(2))), p.ptr, None, None, None))
+                generic = lambda: _ffi.check(getattr(lib, f"ekm_interpolate_monotonic_{tag}")(  # noqa: E731
+                    dev, None, data.ptr, p.ptr, 1, d_t.ptr, 0, nt, npts, nlev, 0, 0, null, null, null, null, 0, out.ptr))
+                pressure()
+                ms = dict(fused=timer.mean(fused), generic=timer.mean(generic), two_step=timer.mean(lambda: (pressure(), generic())),
+                          copy=timer.copy([data.ptr], [out.ptr], out.nbytes))
+                copy_rate = 2 * out.nbytes / (ms["copy"] * 1e-3)
+                run = dict(dtype=tag, ntarget=nt, kernel_ms=ms, copy_bytes_per_s=copy_rate,
+                           fused=part(dt.itemsize * (3 * nt * npts + npts), ms["fused"], copy_rate,
+                                      output_points_per_s=nt * npts / (ms["fused"] * 1e-3)),
+                           generic=part(dt.itemsize * 5 * nt * npts, ms["generic"], copy_rate),
+                           fused_over_two_step=ms["fused"] / ms["two_step"])
+                bl.emit(result, "runs", run)
+                out.free(), d_t.free()
+            for x in (data, p, d_sp, d_a, d_b):
+                x.free()
+    bl.write(args.out, result)
 
 
 if __name__ == "__main__":

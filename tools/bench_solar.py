@@ -3,8 +3,8 @@
 
 Points: `--npts` (default 2^21) and a 0.1-degree global grid (1801 x 3600 = 6 483 600 points), random latitudes in
 [-90, 90] and longitudes in [-180, 180] as full fields, f32 and f64.  Calls: the instantaneous cosine (one node; f32
-input gives f64) and the 24 h average at order 3 (72 nodes; the result in the input dtype).  Every timing is HIP events
-around `--steps` launches after `--warmup`, in ONE process on the same arrays.  Beside each kernel time:
+input gives f64) and the 24 h average at order 3 (72 nodes; the result in the input dtype).  How the timings are taken:
+tools/_benchlib.py.  Beside each kernel time:
   copy_ms   ekm_stream_mix with two streams in and one out of the input arrays' size: a no-arithmetic pass over the
             same arrays (for f32 in -> f64 out the real output is twice that stream);
   numpy_ms  the same call evaluated with plain float64 NumPy on the host, one pass over the points per node as the
@@ -12,20 +12,14 @@ around `--steps` launches after `--warmup`, in ONE process on the same arrays.  
 
 Usage: python tools/bench_solar.py [--steps 10 --warmup 3 --npts 2097152 --out profiles/solar_bench.json]
 """
-import argparse
 import ctypes as C
 import datetime as dt
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "earthkit-meteo_amd"))
+import _benchlib as bl
 
-HBM_PEAK = 8.0e12
 GRID = 1801 * 3600
 DAY = (dt.datetime(2024, 4, 22), dt.datetime(2024, 4, 23))
 NOON = dt.datetime(2024, 4, 22, 12)
@@ -44,74 +38,49 @@ def numpy_seconds(rec, lat, lon):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = bl.parser("solar_bench.json")
     ap.add_argument("--npts", type=int, default=1 << 21)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "solar_bench.json"))
     args = ap.parse_args()
 
     import ekm_hip
     from ekm_hip import _ffi, solar
 
-    lib, dev = _ffi.lib(), 0
-    _ffi.check(lib.ekm_init())
-    name = C.create_string_buffer(128)
-    lib.ekm_device_name(dev, name, 128)
-    result = dict(steps=args.steps, warmup=args.warmup, device=name.value.decode(), hbm_peak_bytes_per_s=HBM_PEAK,
-                  runs=[])
-    ev = [C.c_void_p(), C.c_void_p()]
-    for e in ev:
-        _ffi.check(lib.ekm_event_create(dev, C.byref(e)))
+    lib, dev, name = bl.open_device()
+    result = dict(steps=args.steps, warmup=args.warmup, device=name, hbm_peak_bytes_per_s=bl.HBM_PEAK, runs=[])
 
-    def timed(launch):
-        for _ in range(args.warmup):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[0], None))
-        for _ in range(args.steps):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[1], None))
-        _ffi.check(lib.ekm_event_sync(dev, ev[1]))
-        ms = C.c_float()
-        _ffi.check(lib.ekm_event_elapsed_ms(dev, ev[0], ev[1], C.byref(ms)))
-        return ms.value / args.steps
+    with bl.EventTimer(lib, dev, args.steps, args.warmup) as timer:
+        dates, weights = solar.node_dates(*DAY)
+        records = {"instant": solar.node_records([NOON]), "integrated_24h_order3": solar.node_records(dates, weights)}
+        rng = np.random.default_rng(1)
 
-    dates, weights = solar.node_dates(*DAY)
-    records = {"instant": solar.node_records([NOON]), "integrated_24h_order3": solar.node_records(dates, weights)}
-    rng = np.random.default_rng(1)
-
-    for npts in (args.npts, GRID):
-        lat64, lon64 = rng.uniform(-90, 90, npts), rng.uniform(-180, 180, npts)
-        numpy_s = {k: numpy_seconds(r, lat64, lon64) for k, r in records.items()}
-        for dtype in (np.float32, np.float64):
-            dt_ = np.dtype(dtype)
-            lat, lon = ekm_hip.DeviceArray.from_host(lat64.astype(dt_)), ekm_hip.DeviceArray.from_host(lon64.astype(dt_))
-            scratch = ekm_hip.DeviceArray.empty((npts,), dt_)
-            ops = [_ffi.Operand(a.ptr, _ffi.FIELD, 0, 0, 0) for a in (lat, lon)]
-            ins, outs = (C.c_void_p * 2)(lat.ptr, lon.ptr), (C.c_void_p * 1)(scratch.ptr)
-            copy_ms = timed(lambda: _ffi.check(lib.ekm_stream_mix(dev, None, ins, 2, outs, 1, lat.nbytes)))
-            for what, rec in records.items():
-                out_dt = np.dtype(np.float64) if what == "instant" else dt_
-                entry = "ekm_solar_" + ("f64" if dt_ == np.float64 else "f32_f64" if out_dt == np.float64 else "f32")
-                out = ekm_hip.DeviceArray.empty((npts,), out_dt)
-                nodes = ekm_hip.DeviceArray.from_host(solar.kernel_records(rec))
-                nn = len(rec["w"])
-                fn = getattr(lib, entry)
-                ms = timed(lambda: _ffi.check(fn(dev, None, C.byref(ops[0]), C.byref(ops[1]), nodes.ptr, nn, out.ptr, npts)))
-                nbytes = npts * (2 * dt_.itemsize + out_dt.itemsize)
-                run = dict(dtype=dt_.name, call=what, entry=entry, nnodes=nn, npts=npts, kernel_ms=ms, algorithmic_bytes=nbytes,
-                           bytes_per_s=nbytes / (ms * 1e-3), frac_hbm_peak=nbytes / (ms * 1e-3) / HBM_PEAK, copy_ms=copy_ms,
-                           copy_bytes=3 * lat.nbytes, points_per_s=npts / (ms * 1e-3),
-                           numpy_ms=numpy_s[what] * 1e3)
-                result["runs"].append(run)
-                print(json.dumps(run), flush=True)
-                out.free()
-                nodes.free()
-            for x in (lat, lon, scratch):
-                x.free()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f, indent=1, sort_keys=True)
+        for npts in (args.npts, GRID):
+            lat64, lon64 = rng.uniform(-90, 90, npts), rng.uniform(-180, 180, npts)
+            numpy_s = {k: numpy_seconds(r, lat64, lon64) for k, r in records.items()}
+            for dtype in (np.float32, np.float64):
+                dt_ = np.dtype(dtype)
+                lat, lon = ekm_hip.DeviceArray.from_host(lat64.astype(dt_)), ekm_hip.DeviceArray.from_host(lon64.astype(dt_))
+                scratch = ekm_hip.DeviceArray.empty((npts,), dt_)
+                ops = [_ffi.Operand(a.ptr, _ffi.FIELD, 0, 0, 0) for a in (lat, lon)]
+                copy_ms = timer.copy([lat.ptr, lon.ptr], [scratch.ptr], lat.nbytes)
+                for what, rec in records.items():
+                    out_dt = np.dtype(np.float64) if what == "instant" else dt_
+                    entry = "ekm_solar_" + ("f64" if dt_ == np.float64 else "f32_f64" if out_dt == np.float64 else "f32")
+                    out = ekm_hip.DeviceArray.empty((npts,), out_dt)
+                    nodes = ekm_hip.DeviceArray.from_host(solar.kernel_records(rec))
+                    nn = len(rec["w"])
+                    fn = getattr(lib, entry)
+                    ms = timer.mean(lambda: _ffi.check(fn(dev, None, C.byref(ops[0]), C.byref(ops[1]), nodes.ptr, nn, out.ptr, npts)))
+                    nbytes = npts * (2 * dt_.itemsize + out_dt.itemsize)
+                    d = bl.derived(ms, nbytes, None, npts)
+                    run = dict(dtype=dt_.name, call=what, entry=entry, nnodes=nn, npts=npts, kernel_ms=ms, algorithmic_bytes=nbytes,
+                               bytes_per_s=d["bytes_per_s"], frac_hbm_peak=d["frac_hbm_peak"], copy_ms=copy_ms,
+                               copy_bytes=3 * lat.nbytes, points_per_s=d["points_per_s"], numpy_ms=numpy_s[what] * 1e3)
+                    bl.emit(result, "runs", run)
+                    out.free()
+                    nodes.free()
+                for x in (lat, lon, scratch):
+                    x.free()
+    bl.write(args.out, result)
 
 
 if __name__ == "__main__":

@@ -2,8 +2,8 @@
 """Times the wind kernels (ekm_wind_*, ekm_windrose_*) on one GPU and writes profiles/wind_bench.json.
 
 Elementwise: speed, direction, xy_to_polar, polar_to_xy and coriolis on full fields of a 0.1-degree global grid
-(1801 x 3600 = 6 483 600 points) and of `--big` points (default 2^27), f32 and f64.  Every timing is HIP events around
-`--steps` launches after `--warmup`, in ONE process on the same arrays.  Beside each kernel time:
+(1801 x 3600 = 6 483 600 points) and of `--big` points (default 2^27), f32 and f64.  How the timings are taken:
+tools/_benchlib.py.  Beside each kernel time:
   copy_ms   ekm_stream_mix with as many streams in and out as the call has, of the same size: a no-arithmetic pass;
   ratio     kernel_ms / copy_ms;
   numpy_ms  the same call with NumPy on the host in the same dtype (grid size only), timed once.
@@ -12,17 +12,12 @@ one; np.histogram2d of the same samples beside it.
 
 Usage: python tools/bench_wind.py [--steps 10 --warmup 3 --big 134217728 --out profiles/wind_bench.json]
 """
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "earthkit-meteo_amd"))
+import _benchlib as bl
 
 GRID = 1801 * 3600
 DEG = 180.0 / np.pi
@@ -47,92 +42,67 @@ def numpy_call(what, a, b):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = bl.parser("wind_bench.json")
     ap.add_argument("--big", type=int, default=1 << 27)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wind_bench.json"))
     args = ap.parse_args()
 
     import ekm_hip
     from ekm_hip import _ffi, wind
 
-    lib, dev = _ffi.lib(), 0
-    _ffi.check(lib.ekm_init())
-    name = C.create_string_buffer(128)
-    lib.ekm_device_name(dev, name, 128)
-    result = dict(steps=args.steps, warmup=args.warmup, device=name.value.decode().strip() or "gfx950", elementwise=[], windrose=[])
-    ev = [C.c_void_p(), C.c_void_p()]
-    for e in ev:
-        _ffi.check(lib.ekm_event_create(dev, C.byref(e)))
+    lib, dev, name = bl.open_device()
+    result = dict(steps=args.steps, warmup=args.warmup, device=name.strip() or "gfx950", elementwise=[], windrose=[])
 
-    def timed(launch):
-        for _ in range(args.warmup):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[0], None))
-        for _ in range(args.steps):
-            launch()
-        _ffi.check(lib.ekm_event_record(dev, ev[1], None))
-        _ffi.check(lib.ekm_event_sync(dev, ev[1]))
-        ms = C.c_float()
-        _ffi.check(lib.ekm_event_elapsed_ms(dev, ev[0], ev[1], C.byref(ms)))
-        return ms.value / args.steps
+    with bl.EventTimer(lib, dev, args.steps, args.warmup) as timer:
+        rng = np.random.default_rng(1)
+        # call -> (entry, inputs, mode, outputs wanted)
+        calls = {"speed": ("polar", 2, 0, (1, 0)), "direction": ("polar", 2, 0, (0, 1)), "xy_to_polar": ("polar", 2, 0, (1, 1)),
+                 "polar_to_xy": ("xy", 2, 0, (1, 1)), "coriolis": ("coriolis", 1, 0, (1, 0))}
+        for npts in (GRID, args.big):
+            for dtype in (np.float32, np.float64):
+                dt_ = np.dtype(dtype)
+                host = [rng.normal(0, 12, npts).astype(dt_), rng.uniform(0, 360, npts).astype(dt_)]
+                a, b = (ekm_hip.DeviceArray.from_host(x) for x in host)
+                o0, o1 = ekm_hip.DeviceArray.empty((npts,), dt_), ekm_hip.DeviceArray.empty((npts,), dt_)
+                ops = [_ffi.Operand(x.ptr, _ffi.FIELD, 0, 0, 0) for x in (a, b)]
+                copies = {}
+                for what, (entry, nin, mode, wanted) in calls.items():
+                    nout = sum(wanted)
+                    if (nin, nout) not in copies:
+                        copies[nin, nout] = timer.copy([a.ptr, b.ptr][:nin], [o0.ptr, o1.ptr][:nout], a.nbytes)
+                    fn = getattr(lib, f"ekm_wind_{entry}_" + bl.tag(dt_))
+                    p0, p1 = (o0.ptr if wanted[0] else None), (o1.ptr if wanted[1] else None)
+                    if entry == "coriolis":
+                        ms = timer.mean(lambda: _ffi.check(fn(dev, None, C.byref(ops[0]), p0, npts)))
+                    else:
+                        ms = timer.mean(lambda: _ffi.check(fn(dev, None, C.byref(ops[0]), C.byref(ops[1]), mode, p0, p1, npts)))
+                    nbytes = npts * dt_.itemsize * (nin + nout)
+                    run = dict(call=what, dtype=dt_.name, npts=npts, kernel_ms=ms, copy_ms=copies[nin, nout], ratio=ms / copies[nin, nout],
+                               algorithmic_bytes=nbytes, bytes_per_s=nbytes / (ms * 1e-3),
+                               numpy_ms=numpy_call(what, host[0], host[1]) if npts == GRID else None)
+                    bl.emit(result, "elementwise", run)
+                for x in (a, b, o0, o1):
+                    x.free()
 
-    rng = np.random.default_rng(1)
-    # call -> (entry, inputs, mode, outputs wanted)
-    calls = {"speed": ("polar", 2, 0, (1, 0)), "direction": ("polar", 2, 0, (0, 1)), "xy_to_polar": ("polar", 2, 0, (1, 1)),
-             "polar_to_xy": ("xy", 2, 0, (1, 1)), "coriolis": ("coriolis", 1, 0, (1, 0))}
-    for npts in (GRID, args.big):
+        bins = [0.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0]
+        lon = np.linspace(0, 40 * np.pi, GRID)
+        fields = {"constant": (np.full(GRID, 5.0), np.full(GRID, 200.0)),
+                  "smooth": (10 + 9 * np.sin(lon), 180 + 170 * np.sin(0.37 * lon)),
+                  "random": (rng.uniform(0, 64, GRID), rng.uniform(0, 360, GRID))}
         for dtype in (np.float32, np.float64):
-            dt_ = np.dtype(dtype)
-            host = [rng.normal(0, 12, npts).astype(dt_), rng.uniform(0, 360, npts).astype(dt_)]
-            a, b = (ekm_hip.DeviceArray.from_host(x) for x in host)
-            o0, o1 = ekm_hip.DeviceArray.empty((npts,), dt_), ekm_hip.DeviceArray.empty((npts,), dt_)
-            ops = [_ffi.Operand(x.ptr, _ffi.FIELD, 0, 0, 0) for x in (a, b)]
-            copies = {}
-            for what, (entry, nin, mode, wanted) in calls.items():
-                nout = sum(wanted)
-                if (nin, nout) not in copies:
-                    ins, outs = (C.c_void_p * 2)(a.ptr, b.ptr), (C.c_void_p * 2)(o0.ptr, o1.ptr)
-                    copies[nin, nout] = timed(lambda: _ffi.check(lib.ekm_stream_mix(dev, None, ins, nin, outs, nout, a.nbytes)))
-                fn = getattr(lib, f"ekm_wind_{entry}_" + ("f32" if dt_ == np.float32 else "f64"))
-                p0, p1 = (o0.ptr if wanted[0] else None), (o1.ptr if wanted[1] else None)
-                if entry == "coriolis":
-                    ms = timed(lambda: _ffi.check(fn(dev, None, C.byref(ops[0]), p0, npts)))
-                else:
-                    ms = timed(lambda: _ffi.check(fn(dev, None, C.byref(ops[0]), C.byref(ops[1]), mode, p0, p1, npts)))
-                nbytes = npts * dt_.itemsize * (nin + nout)
-                run = dict(call=what, dtype=dt_.name, npts=npts, kernel_ms=ms, copy_ms=copies[nin, nout], ratio=ms / copies[nin, nout],
-                           algorithmic_bytes=nbytes, bytes_per_s=nbytes / (ms * 1e-3),
-                           numpy_ms=numpy_call(what, host[0], host[1]) if npts == GRID else None)
-                result["elementwise"].append(run)
-                print(json.dumps(run), flush=True)
-            for x in (a, b, o0, o1):
-                x.free()
-
-    bins = [0.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0]
-    lon = np.linspace(0, 40 * np.pi, GRID)
-    fields = {"constant": (np.full(GRID, 5.0), np.full(GRID, 200.0)),
-              "smooth": (10 + 9 * np.sin(lon), 180 + 170 * np.sin(0.37 * lon)),
-              "random": (rng.uniform(0, 64, GRID), rng.uniform(0, 360, GRID))}
-    for dtype in (np.float32, np.float64):
-        for fname, (sp, di) in fields.items():
-            sp, di = sp.astype(dtype), di.astype(dtype)
-            t0 = time.perf_counter()
-            np.histogram2d(sp, di, bins=list(wind.rose_edges(np.dtype(dtype), 16, bins)))
-            numpy_ms = (time.perf_counter() - t0) * 1e3
-            d_sp, d_di = ekm_hip.DeviceArray.from_host(sp), ekm_hip.DeviceArray.from_host(di)
-            run = dict(field=fname, dtype=np.dtype(dtype).name, npts=GRID, sectors=16, speed_bins=len(bins), numpy_ms=numpy_ms)
-            def go():
-                res, db = wind.windrose(d_sp, d_di, sectors=16, speed_bins=bins)
-                res.free(), db.free()
-            run["call_ms"] = timed(go)  # (the whole call: memset, count kernel, finish kernel and the copy of the bins)
-            result["windrose"].append(run)
-            print(json.dumps(run), flush=True)
-            d_sp.free(), d_di.free()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f, indent=1, sort_keys=True)
+            for fname, (sp, di) in fields.items():
+                sp, di = sp.astype(dtype), di.astype(dtype)
+                t0 = time.perf_counter()
+                np.histogram2d(sp, di, bins=list(wind.rose_edges(np.dtype(dtype), 16, bins)))
+                numpy_ms = (time.perf_counter() - t0) * 1e3
+                d_sp, d_di = ekm_hip.DeviceArray.from_host(sp), ekm_hip.DeviceArray.from_host(di)
+                run = dict(field=fname, dtype=np.dtype(dtype).name, npts=GRID, sectors=16, speed_bins=len(bins), numpy_ms=numpy_ms)
+                def go():
+                    res, db = wind.windrose(d_sp, d_di, sectors=16, speed_bins=bins)
+                    res.free(), db.free()
+                run["call_ms"] = timer.mean(go)  # (the whole call: memset, count kernel, finish kernel and the copy of the bins)
+                bl.emit(result, "windrose", run)
+                d_sp.free(), d_di.free()
+    bl.write(args.out, result)
 
 
 if __name__ == "__main__":
