@@ -306,6 +306,46 @@ EKM_HD Out quantile_point(bool col_nan, Sorted s, unsigned lo, unsigned hi, doub
   return en_add(Out(a), en_mul(diff, t));
 }
 
+// The long-axis quantiles (long_quantiles.hip) sort whole-number keys, not floats: the order-preserving image of the
+// float's bits (negative values: every bit flipped; the others: the sign bit set).  The order of the keys is total, so
+// the sorted column is unique whatever network or library sorts it: -0.0 comes before +0.0 (NumPy leaves their order
+// open).  A NaN takes the largest key, which is also what fills the padding slots; no number maps to it (+inf is
+// 0xff80...).  A column with a NaN is flagged and never read, so that its NaNs lose their payload does not matter.
+template <class T>
+struct SortKey;
+template <>
+struct SortKey<float> {
+  using type = unsigned;
+  static constexpr type kMax = 0xffffffffu;
+  static EKM_HD type of(float x) {
+    type u;
+    __builtin_memcpy(&u, &x, sizeof u);
+    return x != x ? kMax : (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  }
+  static EKM_HD float value(type k) {
+    const type u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float x;
+    __builtin_memcpy(&x, &u, sizeof x);
+    return x;
+  }
+};
+template <>
+struct SortKey<double> {
+  using type = unsigned long long;
+  static constexpr type kMax = 0xffffffffffffffffull;
+  static EKM_HD type of(double x) {
+    type u;
+    __builtin_memcpy(&u, &x, sizeof u);
+    return x != x ? kMax : (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  }
+  static EKM_HD double value(type k) {
+    const type u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double x;
+    __builtin_memcpy(&x, &u, sizeof x);
+    return x;
+  }
+};
+
 // ensemble.py:52-77 (Hersbach 2000).  The differences are formed in T, alpha and beta are float64 (xp.zeros), the sum
 // over i = 0..nens runs in order, starting from the i = 0 term.  p2[i] = (i/n)^2, q2[i] = (1 - i/n)^2: nens+1 values.
 template <class T, class Sorted>

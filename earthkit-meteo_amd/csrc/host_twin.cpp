@@ -3,6 +3,7 @@
 // Compiles ops.hpp / thermo_math.hpp with g++ so the exact formulas the gfx950
 // kernels run can be checked against the golden vectors in a container without
 // a GPU.  The product (ekm_hip) never loads this library and has no CPU path.
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -270,6 +271,49 @@ EKM_HOST_QUANTILES(f32, float, float)
 EKM_HOST_QUANTILES(f64, double, double)
 EKM_HOST_QUANTILES(f32_f64, float, double)
 #undef EKM_HOST_QUANTILES
+
+// ---- long-axis quantiles: std::sort on the keys long_quantile_tiles sorts (SortKey), then quantile_point; same arguments
+// as ekm_long_quantiles_* without dev / stream.  The keys order -0.0 before +0.0, so the sorted column is the kernel's ----
+template <class T, class Out>
+static int host_long_quantiles(const T* arr, size_t outer, unsigned m, size_t inner, const double* lo, const double* hi,
+                               const double* w, unsigned nq, int mode, Out* out) {
+  using Key = ekm::SortKey<T>;
+  if (outer == 0 || inner == 0 || nq == 0) return 0;
+  if (mode != ekm::kQuantileSort && mode != ekm::kQuantileLerp) return -3;
+  if (m < 1 || m > 65536 / sizeof(T) || (mode == ekm::kQuantileSort && sizeof(Out) != sizeof(double))) return -2;
+  const size_t npts = outer * inner;
+  std::vector<typename Key::type> keys(m);
+  for (size_t p = 0; p < npts; ++p) {
+    const T* col = ekm::sample_column<T>(arr, m, inner, p);
+    bool has_nan = false;
+    for (unsigned j = 0; j < m; ++j) {
+      const T x = col[(size_t)j * inner];
+      has_nan = has_nan || x != x;
+      keys[j] = Key::of(x);
+    }
+    std::sort(keys.begin(), keys.end());
+    auto s = [&](unsigned j) -> T { return Key::value(keys[j]); };
+    for (unsigned k = 0; k < nq; ++k)
+      out[(size_t)k * npts + p] = ekm::quantile_point<T, Out>(has_nan, s, (unsigned)lo[k], (unsigned)hi[k], w[k], mode);
+  }
+  return 0;
+}
+#define EKM_HOST_LONG_QUANTILES(tag, T, Out)                                                                            \
+  extern "C" int ekm_host_long_quantiles_##tag(const T* arr, size_t outer, unsigned m, size_t inner, const double* lo,  \
+                                               const double* hi, const double* w, unsigned nq, int mode, Out* out) {    \
+    return host_long_quantiles<T, Out>(arr, outer, m, inner, lo, hi, w, nq, mode, out);                                 \
+  }
+EKM_HOST_LONG_QUANTILES(f32, float, float)
+EKM_HOST_LONG_QUANTILES(f64, double, double)
+EKM_HOST_LONG_QUANTILES(f32_f64, float, double)
+#undef EKM_HOST_LONG_QUANTILES
+// (for the tests of the keys themselves: the sorted column as values)
+extern "C" void ekm_host_sort_by_key_f32(float* x, size_t n) {
+  std::sort(x, x + n, [](float a, float b) { return ekm::SortKey<float>::of(a) < ekm::SortKey<float>::of(b); });
+}
+extern "C" void ekm_host_sort_by_key_f64(double* x, size_t n) {
+  std::sort(x, x + n, [](double a, double b) { return ekm::SortKey<double>::of(a) < ekm::SortKey<double>::of(b); });
+}
 
 // ---- Gumbel fit, cdf and ppf: gumbel_*_point of ensemble_point.hpp on the CPU, same arguments as ekm_gumbel_* without
 // dev / stream (the exponentials are this host's libm, the device library's on the GPU) ----

@@ -109,6 +109,7 @@ def _signatures():
     sig["ekm_gumbel_ppf_f64"] = ([i, vp, vp, vp, sz, vp, u32, vp], i)
     for tag in ("f32", "f64", "f32_f64"):
         sig[f"ekm_quantiles_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp, vp, u32, i, vp], i)
+        sig[f"ekm_long_quantiles_{tag}"] = sig[f"ekm_quantiles_{tag}"]
         sig[f"ekm_solar_{tag}"] = ([i, vp, C.POINTER(Operand), C.POINTER(Operand), vp, u32, vp, sz], i)
     for name, (ins, outs, ints, has_eps) in OPS.items():
         for tag, real in (("f32", C.c_float), ("f64", C.c_double)):

@@ -1,5 +1,6 @@
 """`earthkit.meteo.stats.iter_quantiles` on MI355X: the quantiles of a sample axis at every point of an array (reference
-stats/array/quantiles.py:18-84; kernel `quantile_points` in csrc/ensemble.hip).
+stats/array/quantiles.py:18-84; kernel `quantile_points` in csrc/ensemble.hip, and `long_quantile_tiles` in
+csrc/long_quantiles.hip for sample axes beyond 256 / 128 values: `long_quantiles`, below).
 
 `iter_quantiles` keeps the reference's name, argument order, defaults and its being a generator; `quantiles` is this
 project's addition and returns the same rows stacked.  All levels of a call are computed by ONE launch: the point's
@@ -26,6 +27,22 @@ Limits and deviations:
     numpy.quantile on f64 data (the reference casts each level to the integer dtype, i.e. to 0 or 1).
 The first use of a (method, sample count, levels) uploads its position table, which cannot be recorded: call once outside
 an `ekm_hip.graph()` block before recording.
+
+`long_quantiles` / `iter_long_quantiles` (kernel `long_quantile_tiles` in csrc/long_quantiles.hip) are `quantiles` /
+`iter_quantiles` for LONG sample axes: up to 16384 values in f32 and 8192 in f64 (one column, padded to a power of two,
+in 64 KiB of LDS; more raises `EkmError` naming the cap).  Everything above holds for them -- the three methods bit for
+bit, the dtype rules, NaN columns, the input and output types, the errors, the graph rule; the two pairs share one host
+body and one set of position tables.  One workgroup sorts a tile of whole columns with a bitonic network over the
+order-preserving whole-number image of the float bits, then reads every level off the sorted columns with the
+arithmetic of `quantiles`.  Those keys order -0.0 before +0.0, which NumPy's sort leaves open (and the insertion sort of
+`quantiles` keeps as the input has them): in a column that holds both zeros, a level that lands on a zero may differ
+from the reference, and from `quantiles`, in the zero's sign -- the one place where the results are not the reference's
+bits.  Short axes are accepted and give the bits of `quantiles`.
+Which to call: `iter_quantiles` / `quantiles` are the reference's names and stay as they are (their cap is an error, not a
+fallback); for speed, the two kernels are level at 32 samples and `long_quantiles` is the faster from 64 samples up,
+because the per-lane insertion sort is O(m^2): measured on one MI355X at 101 levels (profiles/long_quantiles_bench.json,
+`crossover`), f32 long / short = 0.70 / 0.71 ms at 32 samples (sample axis last; 0.79 / 0.70 ms with it first), 0.49 /
+1.86 ms at 64, 0.48 / 6.8 ms at 128 and 1.85 / 100 ms at 256; f64 0.44 / 0.64 ms at 32 and 0.44 / 6.9 ms at 128.
 
 `GumbelDistribution`, `value_to_return_period` and `return_period_to_value` (reference stats/array/extreme_values.py:24-155;
 kernels `gumbel_fit_points`, `gumbel_cdf_points`, `gumbel_ppf_points` in csrc/ensemble.hip) keep the reference's names,
@@ -105,11 +122,9 @@ def quantile_positions(method, m, qs, dtype):
     return (prev % m).astype(np.float64), (nxt % m).astype(np.float64), gamma.astype(np.float64)
 
 
-@_foreign_aware("arr")
-def quantiles(arr, which=100, axis=0, method="sort"):
-    """Every level of `iter_quantiles(arr, which, axis, method)` stacked along a new leading axis: [nq, ...] with `axis`
-    removed from `arr`'s shape.  The reference has no such function; with `which=100` on an ensemble or a climate sample
-    this is the `clim` that `extreme.sot` and `extreme.efi` take."""
+def _quantiles(arr, which, axis, method, family):
+    """What `quantiles` (family "ekm_quantiles_") and `long_quantiles` ("ekm_long_quantiles_") share: everything but the
+    kernel and its cap."""
     if method not in _METHODS:
         raise ValueError(f"Invalid method {method!r}, expected 'sort', 'numpy_bulk', or 'numpy'")
     arr = _e.as_input(arr)
@@ -136,11 +151,29 @@ def quantiles(arr, which=100, axis=0, method="sort"):
                        lambda: quantile_positions(method, m, qs, dtype))
     d_arr = _e.upload(arr, dtype, device, stream, keep)
     out = DeviceArray.empty((nq,) + rest, out_dtype, device)
-    entry = "ekm_quantiles_" + ("f32" if out_dtype == _F32 else "f64" if dtype == _F64 else "f32_f64")
+    entry = family + ("f32" if out_dtype == _F32 else "f64" if dtype == _F64 else "f32_f64")
     _e._ffi.check(getattr(_e.lib(), entry)(
         device, stream, d_arr.ptr, outer, m, inner, tabs[0].on(stream), tabs[1].on(stream), tabs[2].on(stream), nq,
         QUANTILE_SORT if method == "sort" else QUANTILE_LERP, out.on(stream)))
     return _e.finish(out, _e.on_device(arr))
+
+
+@_foreign_aware("arr")
+def quantiles(arr, which=100, axis=0, method="sort"):
+    """Every level of `iter_quantiles(arr, which, axis, method)` stacked along a new leading axis: [nq, ...] with `axis`
+    removed from `arr`'s shape.  The reference has no such function; with `which=100` on an ensemble or a climate sample
+    this is the `clim` that `extreme.sot` and `extreme.efi` take."""
+    return _quantiles(arr, which, axis, method, "ekm_quantiles_")
+
+
+@_foreign_aware("arr")
+def long_quantiles(arr, which=100, axis=0, method="sort"):
+    """`quantiles` for a long sample axis: up to 16384 values in f32 and 8192 in f64 (more raises `EkmError`), sorted by
+    one workgroup per tile of columns (kernel `long_quantile_tiles`).  Same arguments, methods, dtypes, levels, errors and
+    results; for a sample axis both functions take, the bits are the same, except for the sign of a zero result in a
+    column that holds both -0.0 and +0.0 (module docstring).  With `which=100` on a model-climate sample (say 20 years x
+    9 dates x 11 members = 1980 values) this is the `clim` of `extreme.efi`, `extreme.sot` and `extreme.cpf`."""
+    return _quantiles(arr, which, axis, method, "ekm_long_quantiles_")
 
 
 def _nanaverage_run(axis, ndim, weighted):
@@ -268,7 +301,17 @@ def iter_quantiles(arr, which=100, axis=0, method="sort"):
     spaced levels linspace(0, 1, n + 1), or a list of levels in [0, 1], yielded in the caller's order.  method: 'sort',
     'numpy_bulk' or 'numpy' (module docstring).  One launch computes all levels; level k is then yielded as row k of
     the result, with `arr`'s shape without `axis`."""
-    res = quantiles(arr, which, axis, method)
+    yield from _rows(quantiles(arr, which, axis, method))
+
+
+def iter_long_quantiles(arr, which=100, axis=0, method="sort"):
+    """`iter_quantiles` for a long sample axis (`long_quantiles`): one launch computes all levels, level k is yielded as
+    row k of the one result."""
+    yield from _rows(long_quantiles(arr, which, axis, method))
+
+
+def _rows(res):
+    """The rows of a stacked result: views of the one allocation for a `DeviceArray`."""
     if isinstance(res, DeviceArray):
         n = math.prod(res.shape[1:])
         for k in range(res.shape[0]):

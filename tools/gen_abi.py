@@ -177,7 +177,8 @@ typedef struct ekm_operand {
  *      Crossing Point Forecast ekm_cpf_*; the solar geometry ekm_solar_*; the wind functions
  *      ekm_wind_polar_*, ekm_wind_xy_*, ekm_wind_coriolis_*, ekm_windrose_*; the Gumbel extreme-value fit and its
  *      functions ekm_gumbel_fit_*, ekm_gumbel_cdf_f64, ekm_gumbel_ppf_f64; the reduce family ekm_regimes_project_*,
- *      ekm_regimes_index_*, ekm_pearson_*; the NaN-skipping weighted mean ekm_nanaverage_*, ekm_nanaverage_work_bytes. */
+ *      ekm_regimes_index_*, ekm_pearson_*; the NaN-skipping weighted mean ekm_nanaverage_*, ekm_nanaverage_work_bytes;
+ *      the long-axis quantiles ekm_long_quantiles_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -443,6 +444,23 @@ EKM_API int ekm_quantiles_f64(int dev, void* stream, const double* arr, size_t o
                               const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
 EKM_API int ekm_quantiles_f32_f64(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
                                   const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
+
+/* long_quantiles: the quantiles of ekm_quantiles_* for a LONG sample axis: m <= 16384 (f32 data) / 8192 (f64 data), more
+ * samples return EKM_ERR_ARG naming the cap.  Same arguments, same modes, same position records, same output; one
+ * workgroup sorts a tile of whole columns in LDS (a bitonic network over the order-preserving whole-number image of the
+ * float bits, columns padded to a power of two >= 32) and reads every level off them with the arithmetic of
+ * ekm_quantiles_*.  The results are those of ekm_quantiles_* bit for bit for every m both accept, except that a column
+ * holding both -0.0 and +0.0 is sorted with -0.0 first (the insertion sort of ekm_quantiles_* keeps their input order), so
+ * a level that lands on a zero may differ in the zero's sign.  Short axes are accepted (m >= 1); ekm_quantiles_* is the
+ * faster of the two for short ones (ekm_hip/stats.py gives the measured crossover).
+ * outer * inner == 0 or nq == 0 returns EKM_OK without a launch. */
+EKM_API int ekm_long_quantiles_f32(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
+                                   const double* lo, const double* hi, const double* w, uint32_t nq, int mode, float* out);
+EKM_API int ekm_long_quantiles_f64(int dev, void* stream, const double* arr, size_t outer, uint32_t m, size_t inner,
+                                   const double* lo, const double* hi, const double* w, uint32_t nq, int mode, double* out);
+EKM_API int ekm_long_quantiles_f32_f64(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
+                                       const double* lo, const double* hi, const double* w, uint32_t nq, int mode,
+                                       double* out);
 
 /* Gumbel extreme-value statistics: reference stats/array/extreme_values.py:24-155.
  * ekm_gumbel_fit_*: reference extreme_values.py:44-64 (GumbelDistribution.fit) with the L-moments of
