@@ -315,6 +315,87 @@ extern "C" void ekm_host_sort_by_key_f64(double* x, size_t n) {
   std::sort(x, x + n, [](double a, double b) { return ekm::SortKey<double>::of(a) < ekm::SortKey<double>::of(b); });
 }
 
+// ---- long-axis reductions: std::sort on the keys the tiles of long_ensemble.hip sort, then the *_point call of the kernel's
+// read-out; same arguments as ekm_long_efi_* / ekm_long_sot_* / ekm_long_crps_from_ensemble_* / ekm_long_gumbel_fit_* without
+// dev / stream.  base: the column's first value, `stride` apart; f: the transform of a value before it is keyed ----
+template <class T, class F>
+static bool host_sorted_keys(const T* base, size_t stride, unsigned m, std::vector<typename ekm::SortKey<T>::type>& keys, F f) {
+  bool has_nan = false;
+  for (unsigned j = 0; j < m; ++j) {
+    const T x = f(base[(size_t)j * stride]);
+    has_nan = has_nan || x != x;
+    keys[j] = ekm::SortKey<T>::of(x);
+  }
+  std::sort(keys.begin(), keys.end());
+  return has_nan;
+}
+template <class T>
+static bool host_long_axis_ok(unsigned m, unsigned least) { return m >= least && m <= 65536 / sizeof(T); }
+
+#define EKM_HOST_LONG_ENSEMBLE(tag, T)                                                                                  \
+  extern "C" int ekm_host_long_efi_##tag(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts,       \
+                                         double eps, const double* acosdiff, const double* proddiff,                    \
+                                         const double* acoef, double* out) {                                            \
+    using Key = ekm::SortKey<T>;                                                                                        \
+    if (nclim < 1 || !host_long_axis_ok<T>(nens, 1)) return -2;                                                         \
+    std::vector<Key::type> keys(nens);                                                                                  \
+    for (size_t p = 0; p < npts; ++p) {                                                                                 \
+      const bool has_nan = host_sorted_keys<T>(ens + p, npts, nens, keys, [](T x) -> T { return x; });                  \
+      out[p] = ekm::efi_point<T>(                                                                                       \
+          nclim, nens, has_nan, [&](unsigned i) -> T { return clim[(size_t)i * npts + p]; },                            \
+          [&](unsigned j) -> T { return Key::value(keys[j]); }, acosdiff, proddiff, acoef, eps);                        \
+    }                                                                                                                   \
+    return 0;                                                                                                           \
+  }                                                                                                                     \
+  extern "C" int ekm_host_long_sot_##tag(const T* qc, const T* qc_tail, const T* ens, unsigned nens, size_t npts,       \
+                                         int perc, double eps, T* out) {                                                \
+    using Key = ekm::SortKey<T>;                                                                                        \
+    if (!host_long_axis_ok<T>(nens, 1) || perc < 2 || perc > 98 || perc == 50) return -2;                               \
+    std::vector<Key::type> keys(nens);                                                                                  \
+    const ekm::Percentile<T> pos = ekm::percentile_position<T>(nens, perc);                                             \
+    const bool zero_below = eps > 0.0;                                                                                  \
+    const T teps = T(eps);                                                                                              \
+    for (size_t p = 0; p < npts; ++p) {                                                                                 \
+      const bool has_nan =                                                                                              \
+          host_sorted_keys<T>(ens + p, npts, nens, keys, [&](T x) -> T { return zero_below && x < teps ? T(0) : x; });  \
+      out[p] = ekm::sot_point<T>(qc[p], qc_tail[p], has_nan, [&](unsigned j) -> T { return Key::value(keys[j]); }, pos, \
+                                 eps);                                                                                  \
+    }                                                                                                                   \
+    return 0;                                                                                                           \
+  }                                                                                                                     \
+  extern "C" int ekm_host_long_crps_from_ensemble_##tag(const T* x, const T* y, unsigned nens, size_t npts,             \
+                                                        const double* p2, const double* q2, double* out,                \
+                                                        unsigned char* missing) {                                       \
+    using Key = ekm::SortKey<T>;                                                                                        \
+    if (!host_long_axis_ok<T>(nens, 1)) return -2;                                                                      \
+    std::vector<Key::type> keys(nens);                                                                                  \
+    for (size_t p = 0; p < npts; ++p) {                                                                                 \
+      const bool has_nan = host_sorted_keys<T>(x + p, npts, nens, keys, [](T v) -> T { return v; });                    \
+      const T yp = y[p];                                                                                                \
+      const bool miss = has_nan || yp != yp;                                                                            \
+      const double r = ekm::crps_point<T>(nens, yp, [&](unsigned j) -> T { return Key::value(keys[j]); }, p2, q2);      \
+      out[p] = miss ? ekm::nan_v<double>() : r;                                                                         \
+      if (missing) missing[p] = miss ? 1 : 0;                                                                           \
+    }                                                                                                                   \
+    return 0;                                                                                                           \
+  }                                                                                                                     \
+  extern "C" int ekm_host_long_gumbel_fit_##tag(const T* sample, size_t outer, unsigned m, size_t inner, double* mu,    \
+                                                double* sigma) {                                                        \
+    using Key = ekm::SortKey<T>;                                                                                        \
+    if (outer == 0 || inner == 0) return 0;                                                                             \
+    if (!host_long_axis_ok<T>(m, 2)) return -2;                                                                         \
+    std::vector<Key::type> keys(m);                                                                                     \
+    for (size_t p = 0; p < outer * inner; ++p) {                                                                        \
+      const bool has_nan =                                                                                              \
+          host_sorted_keys<T>(ekm::sample_column<T>(sample, m, inner, p), inner, m, keys, [](T x) -> T { return x; });  \
+      ekm::gumbel_fit_point<T>(m, has_nan, [&](unsigned j) -> T { return Key::value(keys[j]); }, mu[p], sigma[p]);      \
+    }                                                                                                                   \
+    return 0;                                                                                                           \
+  }
+EKM_HOST_LONG_ENSEMBLE(f32, float)
+EKM_HOST_LONG_ENSEMBLE(f64, double)
+#undef EKM_HOST_LONG_ENSEMBLE
+
 // ---- Gumbel fit, cdf and ppf: gumbel_*_point of ensemble_point.hpp on the CPU, same arguments as ekm_gumbel_* without
 // dev / stream (the exponentials are this host's libm, the device library's on the GPU) ----
 template <class T>

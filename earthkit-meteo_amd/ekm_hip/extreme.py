@@ -24,6 +24,25 @@ levels written by a plain crossing are equal.  With `clim` f64 and `ens` f32 the
 except that it compares `epsilon` rounded to f32.
 
 `sot_unsorted` (raises on every call in the reference) is not provided.
+
+`long_efi` / `long_sot` (kernels `long_efi_tiles`, `long_sot_tiles` in csrc/long_ensemble.hip) are `efi` / `sot` for LONG
+member axes: up to 16384 members in f32 and 8192 in f64 (one column, padded to a power of two, in 64 KiB of LDS; more
+raises `EkmError` naming the cap).  Everything above holds for them -- arguments, dtype rules, the mixed-dtype deviation,
+errors, input and output types, the graph rule; each pair shares one host body and one set of coefficient tables.  One
+workgroup sorts a tile of whole columns with the bitonic network of `stats.long_quantiles`, then one lane per column runs
+the arithmetic of `efi` / `sot` over the sorted column (efi streams its climate rows from global memory, once each).  The
+keys of that sort order -0.0 before +0.0, which NumPy's sort leaves open (and the insertion sort of `efi` / `sot` keeps as
+the input has them): in a column that holds both zeros a result may differ from the reference, and from the short
+function, in the sign of a zero -- the one place where the results are not the reference's bits.  Short axes are accepted
+and give the bits of `efi` / `sot`.  `cpf` has no long form: its rows are percentile rows and its 160-KiB path covers
+101 x 51.
+Which to call: `efi` / `sot` are the reference's names and stay as they are (their cap is an error, not a fallback); for
+speed the long forms are the faster at every member count measured, from 32 up, because the per-lane insertion sort is
+O(nens^2): on one MI355X at 2^20 points and 101 climate rows (profiles/long_ensemble_bench.json, `crossover`), f32 long /
+short efi = 0.54 / 0.66 ms at 32 members, 0.96 / 1.53 at 51, 1.02 / 2.55 at 64, 2.2 / 15.6 at 128 and 5.1 / 108 at 256;
+sot 0.12 / 0.28 at 32, 0.28 / 0.95 at 51, 0.72 / 13.7 at 128 and 1.75 / 103 at 256; f64 efi 0.94 / 1.21 at 32, 1.81 / 2.72
+at 51 and 4.3 / 30.7 at 128, sot 0.54 / 1.65 at 51 and 1.42 / 26.7 at 128.  Beyond the short cap, at 2^16 points: f32 efi
+1.0 ms at 512 members and 5.6 ms at 1980, sot 0.31 and 1.6 ms (the NumPy restatement on the host: 1.3 s and 4.7 s for efi).
 """
 import numpy as np
 
@@ -44,10 +63,8 @@ def efi_coefficients(nclim):
     return acosdiff, proddiff, acoef
 
 
-@_foreign_aware("clim", "ens")
-def efi(clim, ens, eps=-0.1):
-    """Extreme Forecast Index (efi.py:16-89).  clim: (nclim, npoints) per-point climatology, sorted or not; ens:
-    (nens, npoints).  Returns float64 (npoints) for f32 and f64 input, NaN where a column of clim or ens holds a NaN."""
+def _efi(clim, ens, eps, family):
+    """What `efi` (family "ekm_efi_") and `long_efi` ("ekm_long_efi_") share: everything but the kernel and its cap."""
     clim, ens = _e.as_input(clim), _e.as_input(ens)
     if len(clim.shape) != 2 or len(ens.shape) != 2:
         raise ValueError(f"efi: clim and ens must be 2-D (nclim, npoints) and (nens, npoints), got {tuple(clim.shape)} and {tuple(ens.shape)}")
@@ -63,10 +80,25 @@ def efi(clim, ens, eps=-0.1):
     d_clim = _e.upload(clim, dtype, device, stream, keep)
     d_ens = _e.upload(ens, dtype, device, stream, keep)
     out = DeviceArray.empty((npts,), np.float64, device)
-    _e._ffi.check(getattr(_e.lib(), f"ekm_efi_{_e.tag_of(dtype)}")(
+    _e._ffi.check(getattr(_e.lib(), family + _e.tag_of(dtype))(
         device, stream, d_clim.ptr, d_ens.ptr, nclim, nens, npts, eps, tabs[0].on(stream), tabs[1].on(stream),
         tabs[2].on(stream), out.on(stream)))
     return _e.finish(out, _e.on_device(clim, ens))
+
+
+@_foreign_aware("clim", "ens")
+def efi(clim, ens, eps=-0.1):
+    """Extreme Forecast Index (efi.py:16-89).  clim: (nclim, npoints) per-point climatology, sorted or not; ens:
+    (nens, npoints).  Returns float64 (npoints) for f32 and f64 input, NaN where a column of clim or ens holds a NaN."""
+    return _efi(clim, ens, eps, "ekm_efi_")
+
+
+@_foreign_aware("clim", "ens")
+def long_efi(clim, ens, eps=-0.1):
+    """`efi` for a long member axis: up to 16384 members in f32 and 8192 in f64 (more raises `EkmError` naming the cap),
+    sorted by one workgroup per tile of columns (kernel `long_efi_tiles`).  Same arguments, dtypes, errors and results;
+    for a member count both functions take, the bits are the same (module docstring: the sign of a zero)."""
+    return _efi(clim, ens, eps, "ekm_long_efi_")
 
 
 @_foreign_aware("clim", "ens")
@@ -103,11 +135,8 @@ def _points_shape(a, b, what):
     return tuple(int(v) for v in a.shape[1:])
 
 
-@_foreign_aware("clim", "ens")
-def sot(clim, ens, perc, eps=-1e4):
-    """Shift of Tails (sot.py:51-103) from the 101 climate percentiles `clim` (101, ...) and the unsorted ensemble `ens`
-    (nens, ...); trailing dimensions are flattened to points.  `perc`: an int in [2, 98], not 50.  The result has the
-    points' shape, in the arithmetic dtype."""
+def _sot(clim, ens, perc, eps, family):
+    """What `sot` (family "ekm_sot_") and `long_sot` ("ekm_long_sot_") share: everything but the kernel and its cap."""
     clim, ens = _e.as_input(clim), _e.as_input(ens)
     if not (isinstance(perc, int) or isinstance(perc, np.int64)) or (perc < 2 or perc > 98):
         raise Exception("Percentile value should be and Integer between 2 and 98, is {}".format(perc))
@@ -131,9 +160,25 @@ def sot(clim, ens, perc, eps=-1e4):
         p_qc, p_tail = d_rows.ptr, d_rows.ptr + npts * dtype.itemsize
     d_ens = _e.upload(ens, dtype, device, stream, keep)
     out = DeviceArray.empty(pts, dtype, device)
-    _e._ffi.check(getattr(_e.lib(), f"ekm_sot_{_e.tag_of(dtype)}")(
+    _e._ffi.check(getattr(_e.lib(), family + _e.tag_of(dtype))(
         device, stream, p_qc, p_tail, d_ens.ptr, nens, npts, perc, eps, out.on(stream)))
     return _e.finish(out, _e.on_device(clim, ens))
+
+
+@_foreign_aware("clim", "ens")
+def sot(clim, ens, perc, eps=-1e4):
+    """Shift of Tails (sot.py:51-103) from the 101 climate percentiles `clim` (101, ...) and the unsorted ensemble `ens`
+    (nens, ...); trailing dimensions are flattened to points.  `perc`: an int in [2, 98], not 50.  The result has the
+    points' shape, in the arithmetic dtype."""
+    return _sot(clim, ens, perc, eps, "ekm_sot_")
+
+
+@_foreign_aware("clim", "ens")
+def long_sot(clim, ens, perc, eps=-1e4):
+    """`sot` for a long member axis: up to 16384 members in f32 and 8192 in f64 (more raises `EkmError` naming the cap),
+    sorted by one workgroup per tile of columns (kernel `long_sot_tiles`).  Same arguments, dtypes, errors and results;
+    for a member count both functions take, the bits are the same (module docstring: the sign of a zero)."""
+    return _sot(clim, ens, perc, eps, "ekm_long_sot_")
 
 
 @_foreign_aware("qc_tail", "qc", "qf")

@@ -11,6 +11,22 @@ nan_policy: "propagate" leaves NaN at points where x or y holds a NaN.  "raise" 
 "missing" flags back to the host, so they wait for the device (and cannot be recorded into a graph); "omit" returns the
 1-D result of the remaining points, compacted on the host also for DeviceArray input (then uploaded again).
 
+`long_crps_from_ensemble` (kernel `long_crps_tiles` in csrc/long_ensemble.hip) is `crps_from_ensemble` for LONG member
+axes: up to 16384 members in f32 and 8192 in f64 (more raises `EkmError` naming the cap).  Same arguments, dtype rule,
+policies, errors, input and output types and graph rule; the two share one host body and one set of weight tables.  One
+workgroup sorts a tile of whole columns with the bitonic network of `stats.long_quantiles`, then one lane per column walks
+the sorted column with the arithmetic of `crps_from_ensemble`, the sum in the same serial order.  The keys of that sort
+order -0.0 before +0.0, which NumPy's sort leaves open: in a column that holds both zeros a result may differ from the
+reference, and from `crps_from_ensemble`, in the sign of a zero -- the one place where the results are not the reference's
+bits.  Short axes are accepted and give the bits of `crps_from_ensemble`.
+Which to call: `crps_from_ensemble` is the reference's name and stays as it is (its cap is an error, not a fallback); for
+speed the long form is the faster at every member count measured, from 32 up, because the per-lane insertion sort is
+O(nens^2): on one MI355X at 2^20 points (profiles/long_ensemble_bench.json, `crossover`), f32 long / short = 0.14 / 0.30 ms
+at 32 members, 0.30 / 0.99 at 51, 0.31 / 1.86 at 64, 0.82 / 14.0 at 128 and 2.3 / 104 at 256; f64 0.24 / 0.53 at 32,
+0.60 / 1.73 at 51 and 1.63 / 27.5 at 128.  Beyond the short cap, at 2^16 points: f32 0.59 ms at 512 members and 6.0 ms at
+1980 (f64 1.1 and 12.1 ms; the NumPy restatement on the host: 0.57 s and 2.6 s) -- at 1980 members the serial walk of one
+lane per column costs three times the sort.
+
 `pearson_correlation(x, y, axis=0)`: the correlation of x and y along `axis`, any axis and any length of it (the kernels
 stream the axis; nothing is uploaded but the operands, so the call can be recorded into a graph).  f32 when x and y are
 both f32, otherwise f64 (integers included), the result in that dtype (the reference works in place on x, so for an
@@ -38,10 +54,9 @@ def crps_weights(n_ens):
     return p**2, (1 - p) ** 2
 
 
-@_foreign_aware("x", "y")
-def crps_from_ensemble(x, y, nan_policy="propagate"):
-    """Continuous Ranked Probability Score of the ensemble x (n_ens, n_points) against y (n_points), Hersbach (2000)
-    (ensemble.py:13-82).  Returns float64 with y's shape ("omit": 1-D, the points without missing values)."""
+def _crps_from_ensemble(x, y, nan_policy, family):
+    """What `crps_from_ensemble` (family "ekm_crps_from_ensemble_") and `long_crps_from_ensemble`
+    ("ekm_long_crps_from_ensemble_") share: everything but the kernel and its cap."""
     if nan_policy not in ["raise", "propagate", "omit"]:
         raise ValueError("Invalid argument: nan_policy must be 'raise', 'propagate', or 'omit'.")
     x, y = _e.as_input(x), _e.as_input(y)
@@ -66,7 +81,7 @@ def crps_from_ensemble(x, y, nan_policy="propagate"):
     if nan_policy != "propagate":
         flags = _Allocation(max(npts, 16), device)
         flags.touch(stream)
-    _e._ffi.check(getattr(_e.lib(), f"ekm_crps_from_ensemble_{_e.tag_of(dtype)}")(
+    _e._ffi.check(getattr(_e.lib(), family + _e.tag_of(dtype))(
         device, stream, d_x.ptr, d_y.ptr, nens, npts, tabs[0].on(stream), tabs[1].on(stream), out.on(stream),
         flags.ptr if flags is not None else None))
     if flags is None:
@@ -83,6 +98,22 @@ def crps_from_ensemble(x, y, nan_policy="propagate"):
         return _e.finish(out, device_result)
     res = _e.finish(out, False).reshape(-1)[~missing]
     return DeviceArray.from_host(res, device) if device_result else res
+
+
+@_foreign_aware("x", "y")
+def crps_from_ensemble(x, y, nan_policy="propagate"):
+    """Continuous Ranked Probability Score of the ensemble x (n_ens, n_points) against y (n_points), Hersbach (2000)
+    (ensemble.py:13-82).  Returns float64 with y's shape ("omit": 1-D, the points without missing values)."""
+    return _crps_from_ensemble(x, y, nan_policy, "ekm_crps_from_ensemble_")
+
+
+@_foreign_aware("x", "y")
+def long_crps_from_ensemble(x, y, nan_policy="propagate"):
+    """`crps_from_ensemble` for a long member axis: up to 16384 members in f32 and 8192 in f64 (more raises `EkmError`
+    naming the cap), sorted by one workgroup per tile of columns (kernel `long_crps_tiles`).  Same arguments, dtypes,
+    policies, errors and results; for a member count both functions take, the bits are the same (module docstring: the
+    sign of a zero)."""
+    return _crps_from_ensemble(x, y, nan_policy, "ekm_long_crps_from_ensemble_")
 
 
 @_foreign_aware("x", "y")

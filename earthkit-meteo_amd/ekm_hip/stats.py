@@ -66,6 +66,19 @@ Deviations of the Gumbel functions:
     reference does); for a device distribution it raises `TypeError`.
 The first use of a set of levels uploads it, which cannot be recorded: call once outside an `ekm_hip.graph()` block.
 
+`GumbelDistribution.long_fit` (kernel `long_gumbel_fit_tiles` in csrc/long_ensemble.hip) is `fit` for LONG sample axes: up to
+16384 values in f32 and 8192 in f64 (more raises `EkmError` naming the cap), any axis.  Same arguments, dtype rules, errors,
+input and output types; it returns the same class, so `cdf`, `ppf`, `value_to_return_period` and `return_period_to_value`
+work on it unchanged, and the two share one host body.  One workgroup sorts a tile of whole columns with the network of
+`long_quantiles`, then one lane per column forms the two sums in float64 in the polyfill's order.  As for `long_quantiles`
+the keys order -0.0 before +0.0: in a column that holds both zeros mu and sigma may differ from `fit`'s in the sign of a
+zero (a sum of zeros); nowhere else.  Short axes are accepted and give the bits of `fit`.
+Which to call: `fit` stays as it is (its cap is an error, not a fallback); for speed `long_fit` is the faster at every
+sample count measured, from 32 up: on one MI355X at 2^20 points, sample axis first (profiles/long_ensemble_bench.json,
+`fit_crossover`), f32 long / short = 0.13 / 0.31 ms at 32 samples, 0.30 / 1.01 at 51, 0.31 / 1.93 at 64, 0.83 / 15.3 at
+128 and 2.1 / 117 at 256; f64 0.23 / 0.53 at 32, 0.61 / 1.78 at 51 and 1.62 / 30.0 at 128.  Beyond the short cap, at 2^16
+points: f32 0.43 ms at 512 samples and 2.8 ms at 1980 (f64 0.79 and 5.3 ms; NumPy on the host: 0.47 s and 2.2 s).
+
 `nanaverage(data, weights=None, **kwargs)` (reference stats/array/numpy_extended.py:13-61; kernels `nanavg_points`,
 `nanavg_rows`, `nanavg_split` in csrc/reduce.hip) is the NaN-skipping, optionally weighted mean along one axis, a run of
 adjacent axes or the whole array.  The data is read once (twice by the weighted mean along a non-contiguous axis) and
@@ -365,6 +378,20 @@ class GumbelDistribution:
     def fit(cls, sample, axis=0, freq=None):
         """Gumbel distribution with parameters fitted to a sample of values along `axis` by the method of L-moments
         (extreme_values.py:44-64).  One launch: every point's samples are sorted in LDS, then summed in float64."""
+        return cls._fit(sample, axis, freq, "ekm_gumbel_fit_")
+
+    @classmethod
+    def long_fit(cls, sample, axis=0, freq=None):
+        """`fit` for a long sample axis: up to 16384 values in f32 and 8192 in f64 (more raises `EkmError` naming the cap),
+        sorted by one workgroup per tile of columns (kernel `long_gumbel_fit_tiles`), then summed in float64 in the same
+        order.  Same arguments, dtypes, errors and results, the same class; for a sample axis both take, the bits are
+        the same (module docstring: the sign of a zero)."""
+        return cls._fit(sample, axis, freq, "ekm_long_gumbel_fit_")
+
+    @classmethod
+    def _fit(cls, sample, axis, freq, family):
+        """What `fit` (family "ekm_gumbel_fit_") and `long_fit` ("ekm_long_gumbel_fit_") share: everything but the kernel
+        and its cap."""
         from . import _engine
 
         (sample,), foreign = _engine._adopt_foreign([sample])
@@ -386,7 +413,7 @@ class GumbelDistribution:
         mu, sigma = DeviceArray.empty(rest, _F64, device), DeviceArray.empty(rest, _F64, device)
         if outer * inner:
             d_sample = _e.upload(sample, dtype, device, stream, keep)
-            _e._ffi.check(getattr(_e.lib(), "ekm_gumbel_fit_" + _e.tag_of(dtype))(
+            _e._ffi.check(getattr(_e.lib(), family + _e.tag_of(dtype))(
                 device, stream, d_sample.ptr, outer, m, inner, mu.on(stream), sigma.on(stream)))
         on_device = _e.on_device(sample)
         dist = cls(_e.finish(mu, on_device), _e.finish(sigma, on_device), freq=freq)

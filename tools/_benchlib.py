@@ -115,6 +115,38 @@ def derived(ms, nbytes, copy_rate, points=None):
     return out
 
 
+def tiled_rows(base, npts, dtype):
+    """[rows, npts] on the device: the distinct columns of `base` [rows, distinct] tiled over the field, row by row."""
+    import ekm_hip
+
+    rows, reps = base.shape[0], (npts + base.shape[1] - 1) // base.shape[1]
+    d = ekm_hip.DeviceArray.empty((rows, npts), dtype)
+    for k in range(rows):
+        d.flat_slice(k * npts, (k + 1) * npts).copy_from_host(np.tile(base[k], reps)[:npts].astype(dtype))
+    return d
+
+
+def one_level_long_quantiles(lib, dev, sample, m, npts, out):
+    """A launch of ekm_long_quantiles_* for the median of `sample` [m, npts] (sample axis first): the tile load and sort of
+    the long-axis kernels with the cheapest read-out there is.  Returns (launch, the tables to keep alive)."""
+    import ekm_hip
+    from ekm_hip import _ffi, stats
+
+    dt = np.dtype(sample.dtype)
+    tabs = [ekm_hip.DeviceArray.from_host(np.ascontiguousarray(t)) for t in stats.quantile_positions("numpy", m, [0.5], dt)]
+    fn = getattr(lib, "ekm_long_quantiles_" + tag(dt))
+    return (lambda: _ffi.check(fn(dev, None, sample.ptr, 1, m, npts, tabs[0].ptr, tabs[1].ptr, tabs[2].ptr, 1, _ffi.QUANTILE_LERP,
+                                  out.ptr))), tabs
+
+
+def merge(path, result):
+    """`write`, keeping the keys another tool wrote into the same file."""
+    if os.path.exists(path):
+        with open(path) as f:
+            result = {**json.load(f), **result}
+    write(path, result)
+
+
 def emit(result, key, run):
     """Appends the run to its list in `result` and prints it as one JSON line."""
     result[key].append(run)

@@ -11,8 +11,17 @@ Beside each time:
                        (the polyfill's loop without its unused third sum), the two exponentials for `cdf`.
 Byte model: fit reads m * itemsize and writes 16 B per point; cdf reads 16 B and writes 8 * nx B per point.
 
+`--long` times GumbelDistribution.long_fit instead and merges two tables into profiles/long_ensemble_bench.json (beside those
+of tools/bench_ensemble.py --long), sample axis first:
+  fit_crossover    f32 and f64 at 2^20 points, 32 / 51 / 64 / 128 / 256 samples: ekm_long_gumbel_fit_* and ekm_gumbel_fit_* on
+                   the same array (the short one refuses 256 samples in f64: null);
+  fit_beyond_cap   512 and 1980 samples at 2^16 points: ekm_long_gumbel_fit_*, ekm_long_quantiles_* with one level on the same
+                   array (the same load and sort: the difference is the serial read-out), and `numpy_fit` on the host, once.
+
 Usage: python tools/bench_gumbel.py [--steps 10 --warmup 3 --out profiles/gumbel_bench.json]
+       python tools/bench_gumbel.py --long [--steps 5 --warmup 2 --out profiles/long_ensemble_bench.json]
 """
+import os
 import time
 
 import numpy as np
@@ -35,8 +44,51 @@ def numpy_fit(sample):
     return b0 - sigma * 0.5772, sigma
 
 
+def long_main(args):
+    import ekm_hip
+    from ekm_hip import _ffi
+
+    lib, dev, name = bl.open_device()
+    result = dict(fit_crossover=[], fit_beyond_cap=[])
+    short_cap = {"f32": 256, "f64": 128}
+    with bl.EventTimer(lib, dev, args.steps, args.warmup) as timer:
+        base = np.random.default_rng(1).gumbel(20.0, 5.0, (1980, DISTINCT))
+        for dtype in (np.float32, np.float64):
+            dt = np.dtype(dtype)
+            tag = bl.tag(dt)
+            for key, npts, counts in (("fit_crossover", 1 << 20, (32, 51, 64, 128, 256)), ("fit_beyond_cap", 1 << 16, (512, 1980))):
+                sample = bl.tiled_rows(base[:max(counts)], npts, dt)  # m rows: a prefix
+                mu, sigma = ekm_hip.DeviceArray.empty((npts,), np.float64), ekm_hip.DeviceArray.empty((npts,), np.float64)
+                out = ekm_hip.DeviceArray.empty((npts,), dt)
+                for m in counts:
+                    def fit(family):
+                        fn = getattr(lib, family + tag)
+                        return lambda: _ffi.check(fn(dev, None, sample.ptr, 1, m, npts, mu.ptr, sigma.ptr))
+                    run = dict(dtype=tag, function="fit", nens=m, npts=npts, long_ms=timer.mean(fit("ekm_long_gumbel_fit_")))
+                    if key == "fit_crossover":
+                        run["short_ms"] = timer.mean(fit("ekm_gumbel_fit_")) if m <= short_cap[tag] else None
+                    else:
+                        sort_launch, keep = bl.one_level_long_quantiles(lib, dev, sample, m, npts, out)
+                        run["long_quantiles_one_level_ms"] = timer.mean(sort_launch)
+                        host = sample.to_host()[:m]
+                        t0 = time.perf_counter()
+                        numpy_fit(host)
+                        run["numpy_ms"] = (time.perf_counter() - t0) * 1e3
+                        del keep
+                    bl.emit(result, key, run)
+                for x in (sample, mu, sigma, out):
+                    x.free()
+    bl.merge(args.out, result)
+
+
 def main():
-    args = bl.parser("gumbel_bench.json").parse_args()
+    ap = bl.parser("gumbel_bench.json")
+    ap.add_argument("--long", action="store_true", help="time GumbelDistribution.long_fit (module docstring)")
+    args = ap.parse_args()
+    if args.long:
+        if args.out.endswith("gumbel_bench.json"):
+            args.out = os.path.join(os.path.dirname(args.out), "long_ensemble_bench.json")
+        return long_main(args)
 
     import ekm_hip
     from ekm_hip import _ffi

@@ -178,7 +178,8 @@ typedef struct ekm_operand {
  *      ekm_wind_polar_*, ekm_wind_xy_*, ekm_wind_coriolis_*, ekm_windrose_*; the Gumbel extreme-value fit and its
  *      functions ekm_gumbel_fit_*, ekm_gumbel_cdf_f64, ekm_gumbel_ppf_f64; the reduce family ekm_regimes_project_*,
  *      ekm_regimes_index_*, ekm_pearson_*; the NaN-skipping weighted mean ekm_nanaverage_*, ekm_nanaverage_work_bytes;
- *      the long-axis quantiles ekm_long_quantiles_*. */
+ *      the long-axis quantiles ekm_long_quantiles_*; the long-axis reductions ekm_long_efi_*, ekm_long_sot_*,
+ *      ekm_long_crps_from_ensemble_*, ekm_long_gumbel_fit_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -461,6 +462,43 @@ EKM_API int ekm_long_quantiles_f64(int dev, void* stream, const double* arr, siz
 EKM_API int ekm_long_quantiles_f32_f64(int dev, void* stream, const float* arr, size_t outer, uint32_t m, size_t inner,
                                        const double* lo, const double* hi, const double* w, uint32_t nq, int mode,
                                        double* out);
+
+/* The sorted-column reductions for a LONG member or sample axis: up to 16384 values in f32 and 8192 in f64, more return
+ * EKM_ERR_ARG naming the cap before anything is read.  Each takes the arguments of its short entry point and gives its
+ * results bit for bit for every axis both accept; one workgroup sorts a tile of whole columns in LDS as
+ * ekm_long_quantiles_* does (the same keys: a column holding both -0.0 and +0.0 is sorted with -0.0 first, so a result
+ * may differ from the short entry point's, and the reference's, in the sign of a zero), then one lane per column runs
+ * the short kernel's per-point arithmetic over it.  Short axes are accepted; ekm_hip/extreme.py, score.py and stats.py
+ * give the measured crossover.  No points returns EKM_OK without a launch.  Only enqueue a kernel: nothing allocates,
+ * copies or waits on the host.
+ * ekm_long_efi_*: reference extreme/array/efi.py:34-89, arguments and result as ekm_efi_*; the climate rows are streamed
+ *   from global memory, once each.
+ * ekm_long_sot_*: reference extreme/array/sot.py:51-103, as ekm_sot_* (members below a positive eps count as 0 before the
+ *   sort).
+ * ekm_long_crps_from_ensemble_*: reference score/array/ensemble.py:34-82, as ekm_crps_from_ensemble_* (missing may be
+ *   NULL).
+ * ekm_long_gumbel_fit_*: reference stats/array/extreme_values.py:44-64 with the L-moments of stats/array/_polyfill.py:14-65,
+ *   as ekm_gumbel_fit_* ([outer, m, inner], m >= 2; the sums in float64 in the polyfill's order). */
+EKM_API int ekm_long_efi_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens,
+                             size_t npts, double eps, const double* acosdiff, const double* proddiff,
+                             const double* acoef, double* out);
+EKM_API int ekm_long_efi_f64(int dev, void* stream, const double* clim, const double* ens, uint32_t nclim, uint32_t nens,
+                             size_t npts, double eps, const double* acosdiff, const double* proddiff,
+                             const double* acoef, double* out);
+EKM_API int ekm_long_sot_f32(int dev, void* stream, const float* qc, const float* qc_tail, const float* ens, uint32_t nens,
+                             size_t npts, int perc, double eps, float* out);
+EKM_API int ekm_long_sot_f64(int dev, void* stream, const double* qc, const double* qc_tail, const double* ens,
+                             uint32_t nens, size_t npts, int perc, double eps, double* out);
+EKM_API int ekm_long_crps_from_ensemble_f32(int dev, void* stream, const float* x, const float* y, uint32_t nens,
+                                            size_t npts, const double* p2, const double* q2, double* out,
+                                            uint8_t* missing);
+EKM_API int ekm_long_crps_from_ensemble_f64(int dev, void* stream, const double* x, const double* y, uint32_t nens,
+                                            size_t npts, const double* p2, const double* q2, double* out,
+                                            uint8_t* missing);
+EKM_API int ekm_long_gumbel_fit_f32(int dev, void* stream, const float* sample, size_t outer, uint32_t m, size_t inner,
+                                    double* mu, double* sigma);
+EKM_API int ekm_long_gumbel_fit_f64(int dev, void* stream, const double* sample, size_t outer, uint32_t m, size_t inner,
+                                    double* mu, double* sigma);
 
 /* Gumbel extreme-value statistics: reference stats/array/extreme_values.py:24-155.
  * ekm_gumbel_fit_*: reference extreme_values.py:44-64 (GumbelDistribution.fit) with the L-moments of
