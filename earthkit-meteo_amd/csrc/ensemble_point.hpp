@@ -285,6 +285,80 @@ EKM_HD float cpf_value(unsigned nclim, unsigned nens, bool from_zero, bool symme
   return value;
 }
 
+// cpf_point in O(nclim + nens) for the long member axes (long_cpf_tiles of long_ensemble.hip): the same arguments,
+// accessors, cursor, three writes and early exit; only the priming step differs.  cpf_point asks, at every row, whether
+// any member iq in [iq0, cross) has ens(iq) >= qc.  Here the members the cursor has passed are folded, once each, into
+// the maximum of the non-NaN ones among them (`top_seen`, valid where `seen`), and the row asks top_seen >= qc.  The two
+// are the same truth value for every qc:
+//  * a NaN member compares false with every qc and is left out of the maximum; if qc is a NaN both sides are false;
+//  * over the non-NaN members, max >= qc holds exactly where some member >= qc holds (the maximum is one of them, and
+//    >= is transitive); -0.0 == +0.0, so which of the two zeros the maximum keeps decides nothing.
+// Nothing in this assumes an order of the members, so it holds for sorted and as-given columns alike, and for the
+// negated, reversed accessors of `symmetric` (they are just another pair of columns).  `primed` never goes back to
+// false and `done` is read as cpf_point reads it, so every write happens at the same (row, member) with the same
+// operands: the result is cpf_point's, bit for bit (tests/test_zz_long_cpf_cpu.py holds the two against each other).
+template <class T, class Clim, class Ens>
+EKM_HD float cpf_point_running(unsigned nclim, unsigned nens, bool from_zero, Clim clim, Ens ens) {
+  float value = 0.0f;
+  bool done = false, primed = false;
+  if (nclim < 3 || nens < 1) return value;
+  const unsigned iq0 = from_zero ? 0u : nens / 2;
+  const unsigned long long dc = nclim - 1, df = (unsigned long long)nens + 1;
+  const T top = clim(nclim - 1);
+  unsigned cross = iq0;
+  T top_seen = T(0);  // the largest non-NaN member of [iq0, cross)
+  bool seen = false;  // there is one
+  for (unsigned icl = 1; icl + 1 < nclim; ++icl) {
+    while (cross < nens && (cross + 1ull) * dc < icl * df) {
+      const T v = ens(cross);
+      if (v == v && (!seen || v > top_seen)) {
+        top_seen = v;
+        seen = true;
+      }
+      ++cross;
+    }
+    if (done && cross >= 2) break;
+    const T qc = clim(icl);
+    if (seen && !done && top_seen >= qc) primed = true;
+    if (cross >= nens) continue;  // no member reaches this row's level
+    const T qf = ens(cross);
+    if (cross < 2) {  // cpf.py:47-62
+      const T qc2 = clim(icl - 1);
+      if (qf < qc && qc2 < qc && primed) {
+        const T tau_c = T((double)icl / ((double)nclim - 1.0)), tau_c2 = T((double)(icl - 1) / (double)(nclim - 1));
+        const double x = (double)cpf_intersection<T>(tau_c, tau_c2, qc, qc2, qf);
+        value = (float)((x > 0.0 || x != x) ? x : 0.0);
+        done = true;
+      }
+    }
+    if (qf < qc && !done && primed) {  // cpf.py:65-67
+      value = (float)(((double)cross + 1.0) / ((double)nens + 1.0));
+      done = true;
+    }
+    if (cross == nens - 1 && qf > qc && top > qc && !done && primed) {  // cpf.py:70-81
+      const T tau_c = T((double)icl / ((double)nclim - 1.0));
+      value = (float)en_min((double)cpf_intersection<T>(tau_c, T(1), qc, top, qf), 1.0);
+    }
+  }
+  return value;
+}
+
+// cpf_value over cpf_point_running
+template <class T, class Clim, class Ens>
+EKM_HD float cpf_value_running(unsigned nclim, unsigned nens, bool from_zero, bool symmetric, bool use_epsilon, T epsilon,
+                               Clim clim, Ens ens) {
+  float value = cpf_point_running<T>(nclim, nens, from_zero, clim, ens);
+  if (symmetric) {
+    if (value < 0.5f)
+      value = en_sub(1.0f, cpf_point_running<T>(
+                               nclim, nens, from_zero, [&](unsigned i) -> T { return -clim(nclim - 1 - i); },
+                               [&](unsigned j) -> T { return -ens(nens - 1 - j); }));
+  } else if (use_epsilon && ens(nens - 1) < epsilon) {
+    value = 0.0f;
+  }
+  return value;
+}
+
 // quantiles.py:60-84: one quantile level of one point.  The position record (lo, hi, w) of the level is computed by the
 // host exactly as the reference (method "sort") or numpy.quantile (methods "numpy_bulk", "numpy") computes it; nothing is
 // floored here.  `mode` is EKM_QUANTILE_SORT / EKM_QUANTILE_LERP of include/ekm_thermo.h:

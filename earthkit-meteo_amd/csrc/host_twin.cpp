@@ -396,6 +396,38 @@ EKM_HOST_LONG_ENSEMBLE(f32, float)
 EKM_HOST_LONG_ENSEMBLE(f64, double)
 #undef EKM_HOST_LONG_ENSEMBLE
 
+// ---- long cpf: the two columns as the keys long_cpf_tiles holds (std::sort where the flag asks for it, the given order
+// otherwise), then cpf_value_running; same arguments as ekm_long_cpf_* without dev / stream ----
+template <class T>
+static int host_long_cpf(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts, int sort_clim,
+                         int sort_ens, int from_zero, int symmetric, int use_epsilon, double epsilon, float* out) {
+  using Key = ekm::SortKey<T>;
+  if (!host_long_axis_ok<T>(nclim, 1) || !host_long_axis_ok<T>(nens, 1)) return -2;
+  std::vector<typename Key::type> ckeys(nclim), ekeys(nens);
+  auto keys_of = [&](const T* base, unsigned m, std::vector<typename Key::type>& keys, int sorted) {
+    for (unsigned j = 0; j < m; ++j) keys[j] = Key::of(base[(size_t)j * npts]);
+    if (sorted) std::sort(keys.begin(), keys.end());
+  };
+  for (size_t p = 0; p < npts; ++p) {
+    keys_of(clim + p, nclim, ckeys, sort_clim);
+    keys_of(ens + p, nens, ekeys, sort_ens);
+    out[p] = ekm::cpf_value_running<T>(
+        nclim, nens, from_zero != 0, symmetric != 0, use_epsilon != 0, T(epsilon),
+        [&](unsigned i) -> T { return Key::value(ckeys[i]); }, [&](unsigned j) -> T { return Key::value(ekeys[j]); });
+  }
+  return 0;
+}
+#define EKM_HOST_LONG_CPF(tag, T)                                                                                         \
+  extern "C" int ekm_host_long_cpf_##tag(const T* clim, const T* ens, unsigned nclim, unsigned nens, size_t npts,         \
+                                         int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,      \
+                                         double epsilon, float* out) {                                                    \
+    return host_long_cpf<T>(clim, ens, nclim, nens, npts, sort_clim, sort_ens, from_zero, symmetric, use_epsilon, epsilon, \
+                            out);                                                                                         \
+  }
+EKM_HOST_LONG_CPF(f32, float)
+EKM_HOST_LONG_CPF(f64, double)
+#undef EKM_HOST_LONG_CPF
+
 // ---- Gumbel fit, cdf and ppf: gumbel_*_point of ensemble_point.hpp on the CPU, same arguments as ekm_gumbel_* without
 // dev / stream (the exponentials are this host's libm, the device library's on the GPU) ----
 template <class T>

@@ -16,6 +16,9 @@
 // The read-out is SERIAL per column: the sums of gumbel_fit_point and crps_point and the cursor of efi_point run in the
 // reference's order, which is what makes them the reference's bits, so a tile of C columns keeps C of the 256 lanes busy
 // (8 at 1980 members in f32).  DESIGN.md section 4 has the measured cost.
+//
+// extreme.long_cpf / ekm_long_cpf_* (reference extreme/array/cpf.py:13-155) is here too: long_cpf_tiles holds TWO tiles,
+// the ensemble's and the climate's, and its read-out is cpf_value_running of ensemble_point.hpp (stated at the kernel).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -115,6 +118,46 @@ __global__ __launch_bounds__(kLongThreads) void long_gumbel_fit_tiles(const T* _
 }
 
 #undef EKM_LONG_TILE
+
+// cpf.py:13-155 for long columns: TWO tiles, the ensemble's (RE keys per thread, columns of 2^log2e slots) and the
+// climate's (RC, 2^log2c), each the small or the full tile of T.  The workgroup takes `columns` = min(columns of the two
+// tiles) whole points; the tile that could hold more treats the rest as dead columns.  A column is sorted where its flag
+// asks for it (SortKey puts every NaN last, as numpy.sort does, and reads it back as a NaN; the scan only compares NaNs)
+// and loaded as given otherwise; both flags are kernel arguments, so every branch round a barrier is uniform.  The scan
+// never reads the NaN flags of the tiles: a column with a NaN does not give NaN in cpf.  Then lane c runs
+// cpf_value_running, O(nclim + nens), over the two columns of point p0 + c.  flags: kCpf* of ensemble_point.hpp.
+// LDS, static: full + full 2 * (64 KiB + 2 KiB of spare slots + 2 KiB of flags) = 136 KiB, full + small 85 KiB,
+// small + small 34 KiB.
+template <class T, int RE, int RC>
+__global__ __launch_bounds__(kLongThreads) void long_cpf_tiles(const T* __restrict__ clim, const T* __restrict__ ens,
+                                                               unsigned nclim, unsigned nens, unsigned log2c,
+                                                               unsigned log2e, unsigned magic_c, unsigned magic_e,
+                                                               unsigned columns, unsigned long long npts, unsigned flags,
+                                                               T epsilon, float* __restrict__ out) {
+  using Key = SortKey<T>;
+  using K = typename Key::type;
+  __shared__ K lds_e[LongTile<RE>::kSlots];
+  __shared__ K lds_c[LongTile<RC>::kSlots];
+  __shared__ unsigned nan_e[LongTile<RE>::kFlags];
+  __shared__ unsigned nan_c[LongTile<RC>::kFlags];
+  const unsigned t = threadIdx.x;
+  const unsigned long long p0 = (unsigned long long)blockIdx.x * columns;
+  const unsigned live = npts - p0 < columns ? (unsigned)(npts - p0) : columns;
+  auto same = [](T x) -> T { return x; };
+  if (flags & kCpfSortEns)
+    long_tile_columns<T, RE>(ens, nens, log2e, magic_e, npts, p0, live, lds_e, nan_e, same);
+  else
+    long_tile_columns_as_given<T, RE>(ens, nens, log2e, magic_e, npts, p0, live, lds_e, nan_e, same);
+  if (flags & kCpfSortClim)
+    long_tile_columns<T, RC>(clim, nclim, log2c, magic_c, npts, p0, live, lds_c, nan_c, same);
+  else
+    long_tile_columns_as_given<T, RC>(clim, nclim, log2c, magic_c, npts, p0, live, lds_c, nan_c, same);
+  if (t < live)  // (columns <= 128: a small tile holds at most 4096 / 32 of them)
+    out[p0 + t] = cpf_value_running<T>(
+        nclim, nens, (flags & kCpfFromZero) != 0, (flags & kCpfSymmetric) != 0, (flags & kCpfEpsilon) != 0, epsilon,
+        [&](unsigned i) -> T { return Key::value(lds_c[long_slot((t << log2c) + i, log2c)]); },
+        [&](unsigned i) -> T { return Key::value(lds_e[long_slot((t << log2e) + i, log2e)]); });
+}
 
 // The tile of a launch: the padded column, which of the two tile sizes holds it, the grid, the divisor of the tile load
 struct LongShape {
@@ -224,6 +267,33 @@ static int launch_long_gumbel_fit(int dev, void* stream, const T* sample, size_t
   return launched("long_gumbel_fit");
 }
 
+// The two axes are held to the cap separately; the workgroup takes as many points as the tile with fewer columns holds
+template <class T>
+static int launch_long_cpf(int dev, void* stream, const T* clim, const T* ens, uint32_t nclim, uint32_t nens, size_t npts,
+                           int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon, double epsilon,
+                           float* out) {
+  if (npts == 0) return EKM_OK;
+  int rc = check_pointers("long_cpf", sizeof(float), {out});
+  if (rc != EKM_OK) return rc;
+  LongShape se, sc;
+  if ((rc = long_prepare<T>(dev, "long_cpf", "members", npts, nens, 1, {ens}, &se)) != EKM_OK) return rc;
+  if ((rc = long_prepare<T>(dev, "long_cpf", "climate rows", npts, nclim, 1, {clim}, &sc)) != EKM_OK) return rc;
+  constexpr unsigned kCap = kLongKeyBytes / sizeof(T), kSmall = kLongSmallKeyBytes / sizeof(T);
+  const unsigned cols_e = (se.small ? kSmall : kCap) >> se.log2n, cols_c = (sc.small ? kSmall : kCap) >> sc.log2n;
+  const unsigned columns = cols_e < cols_c ? cols_e : cols_c;
+  unsigned grid;
+  if ((rc = launch_grid("long_cpf", npts, columns, &grid)) != EKM_OK) return rc;
+  const unsigned flags = cpf_flags(sort_clim, sort_ens, from_zero, symmetric, use_epsilon);
+  long_dispatch<T>(se.small, [&](auto re) {
+    long_dispatch<T>(sc.small, [&](auto rcl) {
+      hipLaunchKernelGGL((long_cpf_tiles<T, decltype(re)::value, decltype(rcl)::value>), dim3(grid), dim3(kLongThreads), 0,
+                         static_cast<hipStream_t>(stream), clim, ens, nclim, nens, sc.log2n, se.log2n, sc.magic, se.magic,
+                         columns, (unsigned long long)npts, flags, T(epsilon), out);
+    });
+  });
+  return launched("long_cpf");
+}
+
 }  // namespace ekm
 
 extern "C" {
@@ -264,6 +334,19 @@ int ekm_long_gumbel_fit_f32(int dev, void* stream, const float* sample, size_t o
 int ekm_long_gumbel_fit_f64(int dev, void* stream, const double* sample, size_t outer, uint32_t m, size_t inner,
                             double* mu, double* sigma) {
   return ekm::launch_long_gumbel_fit<double>(dev, stream, sample, outer, m, inner, mu, sigma);
+}
+
+int ekm_long_cpf_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens,
+                     size_t npts, int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,
+                     double epsilon, float* out) {
+  return ekm::launch_long_cpf<float>(dev, stream, clim, ens, nclim, nens, npts, sort_clim, sort_ens, from_zero, symmetric,
+                                     use_epsilon, epsilon, out);
+}
+int ekm_long_cpf_f64(int dev, void* stream, const double* clim, const double* ens, uint32_t nclim, uint32_t nens,
+                     size_t npts, int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,
+                     double epsilon, float* out) {
+  return ekm::launch_long_cpf<double>(dev, stream, clim, ens, nclim, nens, npts, sort_clim, sort_ens, from_zero, symmetric,
+                                      use_epsilon, epsilon, out);
 }
 
 }  // extern "C"

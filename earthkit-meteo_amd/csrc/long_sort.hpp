@@ -5,7 +5,8 @@
 //   long_tile_load_run / long_tile_load_strided
 //                      the samples to keys in LDS with the per-column NaN flag, a per-element transform applied first;
 //   long_tile_sort     the keys to registers, the network, the sorted keys back to LDS.
-// long_tile_columns runs them in order for a kernel whose array is [outer, m, inner].
+// long_tile_columns runs them in order for a kernel whose array is [outer, m, inner]; long_tile_columns_as_given pads
+// and loads without the network (a column used in the order the array has it: cpf with a sort flag off).
 //
 // Tile: E = 256 * R keys (256 threads, R keys per thread in registers).  A column is padded to n = 2^k >= max(m, 32)
 // slots with the largest key, so a tile holds C = E / n columns, each n-aligned: the network runs over the tile's index
@@ -201,6 +202,23 @@ __device__ __forceinline__ void long_tile_columns(const T* __restrict__ arr, uns
   else
     long_tile_load_strided<T, R>(arr, m, inner, p0, live, log2n, lds, col_nan, t, f);
   long_tile_sort<typename SortKey<T>::type, R>(lds, t, log2n);
+}
+
+// The same tile WITHOUT the network: afterwards column c < live holds its m values in the order the array has them (a
+// key reads back every non-NaN value bit for bit and a NaN as a NaN), and col_nan[c] is set as above.  Ends with a
+// barrier, as long_tile_sort does.
+template <class T, int R, class F>
+__device__ __forceinline__ void long_tile_columns_as_given(const T* __restrict__ arr, unsigned m, unsigned log2n,
+                                                           unsigned magic, unsigned long long inner,
+                                                           unsigned long long p0, unsigned live,
+                                                           typename SortKey<T>::type* lds, unsigned* col_nan, F f) {
+  const unsigned t = threadIdx.x;
+  long_tile_pad<T, R>(lds, col_nan, t, m, log2n, live);
+  if (inner == 1)
+    long_tile_load_run<T>(arr + p0 * m, live * m, m, log2n, magic, lds, col_nan, t, f);
+  else
+    long_tile_load_strided<T, R>(arr, m, inner, p0, live, log2n, lds, col_nan, t, f);
+  __syncthreads();
 }
 
 }  // namespace ekm

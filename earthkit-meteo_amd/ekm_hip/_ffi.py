@@ -100,7 +100,7 @@ def _signatures():
         sig[f"ekm_wind_coriolis_{tag}"] = ([i, vp, op, vp, sz], i)
         sig[f"ekm_windrose_{tag}"] = ([i, vp, vp, vp, sz, vp, u32, u32, dbl, i, vp, vp], i)
         sig[f"ekm_gumbel_fit_{tag}"] = ([i, vp, vp, sz, u32, sz, vp, vp], i)
-        for name in ("efi", "sot", "crps_from_ensemble", "gumbel_fit"):  # the long-axis entries take the short ones' arguments
+        for name in ("efi", "sot", "crps_from_ensemble", "gumbel_fit", "cpf"):  # the long-axis entries take the short ones' arguments
             sig[f"ekm_long_{name}_{tag}"] = sig[f"ekm_{name}_{tag}"]
         sig[f"ekm_regimes_project_{tag}"] = ([i, vp, vp, sz, sz, vp, u32, sz, vp, vp], i)
         sig[f"ekm_regimes_index_{tag}"] = ([i, vp, vp, vp, real, vp, real, vp, sz], i)

@@ -34,8 +34,17 @@ the arithmetic of `efi` / `sot` over the sorted column (efi streams its climate 
 keys of that sort order -0.0 before +0.0, which NumPy's sort leaves open (and the insertion sort of `efi` / `sot` keeps as
 the input has them): in a column that holds both zeros a result may differ from the reference, and from the short
 function, in the sign of a zero -- the one place where the results are not the reference's bits.  Short axes are accepted
-and give the bits of `efi` / `sot`.  `cpf` has no long form: its rows are percentile rows and its 160-KiB path covers
-101 x 51.
+and give the bits of `efi` / `sot`.
+`long_cpf` (kernel `long_cpf_tiles`, same file) is `cpf` for long columns: up to 16384 members AND up to 16384 climate rows
+in f32, 8192 each in f64, checked separately and whether or not they are sorted (`EkmError` naming the axis and the cap),
+so a raw model-climate sample (the 1980 values `stats.long_quantiles` was built for) is a legitimate `clim`.  Everything
+said of `cpf` holds -- arguments, dtype rules, the mixed-dtype deviation, the float32 result, errors, input and output
+types, the graph rule; the two share one host body.  One workgroup holds a tile of ensemble columns and a tile of climate
+columns, sorts each where its flag asks for it (a NaN last, as numpy.sort puts it) or loads it as given, then one lane per
+point scans them in O(nclim + nens) with a running maximum in place of `cpf`'s O(nclim * nens) priming loop: the same
+writes at the same members, so the bits of `cpf` and of the reference.  The zero-sign exception stated for `long_efi`
+applies to a SORTED column that holds both zeros (the key sort orders -0.0 before +0.0): an interpolated value may then
+differ in the sign of a zero.
 Which to call: `efi` / `sot` are the reference's names and stay as they are (their cap is an error, not a fallback); for
 speed the long forms are the faster at every member count measured, from 32 up, because the per-lane insertion sort is
 O(nens^2): on one MI355X at 2^20 points and 101 climate rows (profiles/long_ensemble_bench.json, `crossover`), f32 long /
@@ -43,6 +52,13 @@ short efi = 0.54 / 0.66 ms at 32 members, 0.96 / 1.53 at 51, 1.02 / 2.55 at 64, 
 sot 0.12 / 0.28 at 32, 0.28 / 0.95 at 51, 0.72 / 13.7 at 128 and 1.75 / 103 at 256; f64 efi 0.94 / 1.21 at 32, 1.81 / 2.72
 at 51 and 4.3 / 30.7 at 128, sot 0.54 / 1.65 at 51 and 1.42 / 26.7 at 128.  Beyond the short cap, at 2^16 points: f32 efi
 1.0 ms at 512 members and 5.6 ms at 1980, sot 0.31 and 1.6 ms (the NumPy restatement on the host: 1.3 s and 4.7 s for efi).
+`cpf` or `long_cpf`: `cpf` is the reference's name and stays as it is.  For speed, at 2^20 points and 101 sorted climate
+rows (profiles/long_cpf_bench.json, `crossover`; long / short ms) the long form wins from 51 members up under every
+option set -- f32 default 2.42 / 4.00 at 51, 2.50 / 10.8 at 64, 2.75 / 34.2 at 128, 6.19 / 248 at 256; f64 4.71 / 7.93 at
+51, 5.35 / 68.6 at 128 -- ties at 32 (f32 2.32 / 2.32) and LOSES at 32 members with `sort_clim=False` (f32 1.81 / 1.36, f64
+3.30 / 1.38; at 51 it wins again, 1.90 / 2.26): the short kernel then streams the climate with every lane busy, while the
+long one runs its scan on the 32 (f64 16) lanes of 256 that have a column.  Beyond `cpf`'s cap, at 2^16 points with an
+unsorted climate sample: f32 6.7 ms at 101 x 1980, 21.8 at 1980 x 51, 26.5 at 1980 x 1980 (f64 13.5, 42.3, 52.9).
 """
 import numpy as np
 
@@ -101,13 +117,8 @@ def long_efi(clim, ens, eps=-0.1):
     return _efi(clim, ens, eps, "ekm_long_efi_")
 
 
-@_foreign_aware("clim", "ens")
-def cpf(clim, ens, sort_clim=True, sort_ens=True, epsilon=None, symmetric=False, from_zero=False):
-    """Crossing Point Forecast (cpf.py:94-155).  clim: (nclim, npoints) per-point climatology; ens: (nens, npoints).
-    sort_clim / sort_ens: sort the columns first (a NaN goes last, as numpy.sort puts it), else they are used as given.
-    epsilon: points whose last member is below it give 0; ignored when `symmetric`.  symmetric: values below 0.5 become
-    1 - (the CPF of the negated fields).  from_zero: look for the crossing from the lowest member, not from the median.
-    Returns float32 (npoints); one kernel launch per call.  The inputs are never written."""
+def _cpf(clim, ens, sort_clim, sort_ens, epsilon, symmetric, from_zero, family):
+    """What `cpf` (family "ekm_cpf_") and `long_cpf` ("ekm_long_cpf_") share: everything but the kernel and its caps."""
     clim, ens = _e.as_input(clim), _e.as_input(ens)
     if len(clim.shape) != 2 or len(ens.shape) != 2:
         raise ValueError(f"cpf: clim and ens must be 2-D (nclim, npoints) and (nens, npoints), got {tuple(clim.shape)} and {tuple(ens.shape)}")
@@ -122,11 +133,31 @@ def cpf(clim, ens, sort_clim=True, sort_ens=True, epsilon=None, symmetric=False,
     d_clim = _e.upload(clim, dtype, device, stream, keep)
     d_ens = _e.upload(ens, dtype, device, stream, keep)
     out = DeviceArray.empty((npts,), _F32, device)
-    _e._ffi.check(getattr(_e.lib(), f"ekm_cpf_{_e.tag_of(dtype)}")(
+    _e._ffi.check(getattr(_e.lib(), family + _e.tag_of(dtype))(
         device, stream, d_clim.ptr, d_ens.ptr, nclim, nens, npts, int(bool(sort_clim)), int(bool(sort_ens)),
         int(bool(from_zero)), int(bool(symmetric)), int(use_epsilon), float(epsilon) if use_epsilon else 0.0,
         out.on(stream)))
     return _e.finish(out, _e.on_device(clim, ens))
+
+
+@_foreign_aware("clim", "ens")
+def cpf(clim, ens, sort_clim=True, sort_ens=True, epsilon=None, symmetric=False, from_zero=False):
+    """Crossing Point Forecast (cpf.py:94-155).  clim: (nclim, npoints) per-point climatology; ens: (nens, npoints).
+    sort_clim / sort_ens: sort the columns first (a NaN goes last, as numpy.sort puts it), else they are used as given.
+    epsilon: points whose last member is below it give 0; ignored when `symmetric`.  symmetric: values below 0.5 become
+    1 - (the CPF of the negated fields).  from_zero: look for the crossing from the lowest member, not from the median.
+    Returns float32 (npoints); one kernel launch per call.  The inputs are never written."""
+    return _cpf(clim, ens, sort_clim, sort_ens, epsilon, symmetric, from_zero, "ekm_cpf_")
+
+
+@_foreign_aware("clim", "ens")
+def long_cpf(clim, ens, sort_clim=True, sort_ens=True, epsilon=None, symmetric=False, from_zero=False):
+    """`cpf` for long columns: up to 16384 members AND up to 16384 climate rows in f32, 8192 each in f64, whether they
+    are sorted or not (one more of either raises `EkmError` naming the axis and the cap) -- a raw model-climate sample
+    is a legitimate `clim`.  One workgroup sorts a tile of ensemble columns and a tile of climate columns (kernel
+    `long_cpf_tiles`), then one lane per point scans them in O(nclim + nens).  Same arguments, dtypes, errors and
+    results; for columns both functions take, the bits are the same (module docstring: the sign of a zero)."""
+    return _cpf(clim, ens, sort_clim, sort_ens, epsilon, symmetric, from_zero, "ekm_long_cpf_")
 
 
 def _points_shape(a, b, what):

@@ -12,8 +12,19 @@ field.  How the timings are taken: tools/_benchlib.py.
   copy           ekm_stream_mix, one stream in and one out over the ensemble array: the float4-copy rate the memory
                  system gives these arrays; `copy_ms_same_bytes` is the time that rate needs for the kernel's bytes.
 
+`--long` times extreme.long_cpf instead and writes profiles/long_cpf_bench.json:
+  crossover    f32 and f64 at 2^20 points, 101 climate rows, 32 / 51 / 64 / 128 / 256 members: ekm_long_cpf_* and ekm_cpf_*
+               on the same arrays under the default options, `symmetric`, `from_zero` and sort_clim off (null where the
+               short entry point refuses the shape), and ekm_long_quantiles_* with one level on the ensemble array: the
+               load and sort of one tile with the cheapest read-out there is;
+  beyond_cap   (nclim, nens) = (101, 1980), (1980, 51), (1980, 1980) at 2^16 points: the long entry point and the same
+               one-level long_quantiles; the climate is then a raw sample, unsorted.
+
 Usage: python tools/bench_cpf.py [--steps 10 --warmup 3 --npts 2097152 --out profiles/cpf_bench.json]
+       python tools/bench_cpf.py --long [--steps 5 --warmup 2 --out profiles/long_cpf_bench.json]
 """
+import os
+
 import numpy as np
 
 import _benchlib as bl
@@ -21,10 +32,64 @@ import _benchlib as bl
 NCLIM, NENS, DISTINCT = 101, 51, 1 << 16
 
 
+LONG_OPTIONS = dict(default=(1, 0, 0), symmetric=(1, 0, 1), from_zero=(1, 1, 0), clim_given=(0, 0, 0))  # sort_clim, from_zero, symmetric
+
+
+def long_main(args):
+    import ekm_hip
+    from ekm_hip import _ffi
+
+    lib, dev, name = bl.open_device()
+    result = dict(steps=args.steps, warmup=args.warmup, device=name, crossover=[], beyond_cap=[])
+
+    def launch_of(prefix, tag, clim, ens, nclim, nens, npts, out, option):
+        """A launch of family `prefix` on the first `nens` rows of `ens`, or None where the entry point refuses the shape."""
+        fn, (sort_clim, from_zero, symmetric) = getattr(lib, f"{prefix}cpf_{tag}"), LONG_OPTIONS[option]
+        call = lambda: fn(dev, None, clim.ptr, ens.ptr, nclim, nens, npts, sort_clim, 1, from_zero, symmetric, 0, 0.0, out.ptr)  # noqa: E731
+        if call() == _ffi.EKM_ERR_ARG:
+            return None
+        return lambda: _ffi.check(call())
+
+    with bl.EventTimer(lib, dev, args.steps, args.warmup) as timer:
+        rng = np.random.default_rng(1)
+        for key, npts, distinct, shapes in (("crossover", 1 << 20, 1 << 14, [(NCLIM, m) for m in (32, 51, 64, 128, 256)]),
+                                            ("beyond_cap", 1 << 16, 1 << 12, [(101, 1980), (1980, 51), (1980, 1980)])):
+            rows_c, rows_e = max(c for c, _ in shapes), max(e for _, e in shapes)
+            base_c = np.round(rng.normal(0, 3, (rows_c, distinct)) * 16) / 16 + 0.0
+            base_e = np.round((rng.normal(0, 3, (rows_e, distinct)) + rng.normal(0, 2, distinct)) * 16) / 16 + 0.0
+            if key == "crossover":
+                base_c = np.sort(base_c, axis=0)
+            for dtype in (np.float32, np.float64):
+                dt = np.dtype(dtype)
+                tag = bl.tag(dt)
+                clim, ens = bl.tiled_rows(base_c, npts, dt), bl.tiled_rows(base_e, npts, dt)
+                out, qout = ekm_hip.DeviceArray.empty((npts,), np.float32), ekm_hip.DeviceArray.empty((npts,), dt)
+                for nclim, nens in shapes:
+                    sort_launch, keep = bl.one_level_long_quantiles(lib, dev, ens, nens, npts, qout)
+                    sort_ms = timer.mean(sort_launch)
+                    for option in (LONG_OPTIONS if key == "crossover" else ("default", "symmetric")):
+                        common = (tag, clim, ens, nclim, nens, npts, out, option)
+                        run = dict(dtype=tag, nclim=nclim, nens=nens, npts=npts, options=option,
+                                   long_ms=timer.mean(launch_of("ekm_long_", *common)), long_quantiles_one_level_ms=sort_ms)
+                        if key == "crossover":
+                            short = launch_of("ekm_", *common)
+                            run["short_ms"] = timer.mean(short) if short else None
+                        bl.emit(result, key, run)
+                    del keep
+                for x in (clim, ens, out, qout):
+                    x.free()
+    bl.write(args.out, result)
+
+
 def main():
     ap = bl.parser("cpf_bench.json")
     ap.add_argument("--npts", type=int, default=1 << 21)
+    ap.add_argument("--long", action="store_true", help="time extreme.long_cpf beside cpf (module docstring)")
     args = ap.parse_args()
+    if args.long:
+        if args.out.endswith("cpf_bench.json") and not args.out.endswith("long_cpf_bench.json"):
+            args.out = os.path.join(os.path.dirname(args.out), "long_cpf_bench.json")
+        return long_main(args)
 
     import ekm_hip
     from ekm_hip import _ffi, extreme

@@ -179,7 +179,7 @@ typedef struct ekm_operand {
  *      functions ekm_gumbel_fit_*, ekm_gumbel_cdf_f64, ekm_gumbel_ppf_f64; the reduce family ekm_regimes_project_*,
  *      ekm_regimes_index_*, ekm_pearson_*; the NaN-skipping weighted mean ekm_nanaverage_*, ekm_nanaverage_work_bytes;
  *      the long-axis quantiles ekm_long_quantiles_*; the long-axis reductions ekm_long_efi_*, ekm_long_sot_*,
- *      ekm_long_crps_from_ensemble_*, ekm_long_gumbel_fit_*. */
+ *      ekm_long_crps_from_ensemble_*, ekm_long_gumbel_fit_*, ekm_long_cpf_*. */
 #define EKM_ABI_VERSION 5
 EKM_API int ekm_abi_version(void);              /* EKM_ABI_VERSION of the library as built */
 
@@ -499,6 +499,19 @@ EKM_API int ekm_long_gumbel_fit_f32(int dev, void* stream, const float* sample, 
                                     double* mu, double* sigma);
 EKM_API int ekm_long_gumbel_fit_f64(int dev, void* stream, const double* sample, size_t outer, uint32_t m, size_t inner,
                                     double* mu, double* sigma);
+/* ekm_long_cpf_*: reference extreme/array/cpf.py:13-155, arguments, flags and result as ekm_cpf_* (out: float [npts]), for
+ * LONG columns: nens and nclim EACH up to 16384 (_f32) / 8192 (_f64), checked separately; one more returns EKM_ERR_ARG with
+ * a message that names the axis, its length and the cap, and writes nothing; nens >= 1 and nclim >= 1.  One workgroup holds
+ * a tile of ensemble columns and a tile of climate columns in LDS (each the 16-KiB or the 64-KiB tile, by its own padded
+ * column), sorts each where its flag asks for it -- a NaN above every number, as numpy.sort puts it -- or loads it as given,
+ * then one lane per point runs the scan of ekm_cpf_* in O(nclim + nens) (cpf_point_running of csrc/ensemble_point.hpp:
+ * the bits of ekm_cpf_* on what both take, but for the sign of a zero in a sorted column that holds both zeros). */
+EKM_API int ekm_long_cpf_f32(int dev, void* stream, const float* clim, const float* ens, uint32_t nclim, uint32_t nens,
+                             size_t npts, int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,
+                             double epsilon, float* out);
+EKM_API int ekm_long_cpf_f64(int dev, void* stream, const double* clim, const double* ens, uint32_t nclim, uint32_t nens,
+                             size_t npts, int sort_clim, int sort_ens, int from_zero, int symmetric, int use_epsilon,
+                             double epsilon, float* out);
 
 /* Gumbel extreme-value statistics: reference stats/array/extreme_values.py:24-155.
  * ekm_gumbel_fit_*: reference extreme_values.py:44-64 (GumbelDistribution.fit) with the L-moments of
